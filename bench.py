@@ -1,7 +1,8 @@
 #!/usr/bin/env python
-"""bench.py -- generator images/sec at 512^2 on N MI355X (one process per GPU) + kernel rooflines.
+"""bench.py -- generator images/sec at 512^2 on N MI355X (one process per GPU); with --full also kernel rooflines, side workloads,
+the in-run oracle check and the CPU baselines.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,12 +12,14 @@ is BASELINE.json config 3: 512x512 output, 96x96 rays, 64 samples per ray, batch
 reference's native 512x256 aspect is reported next to it as extra.native_512x256).  Inference shards over the batch
 with no data-path collective: weak scaling, value = all images of all ranks / max-over-ranks time.
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times exactly --steps steps and prints ONE JSON line on rank 0; --dump-outputs DIR writes the
+arrays the last timed step returned as DIR/<name>.npy.  Everything else runs only with --full.
 """
 import argparse
 import importlib
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -122,9 +125,26 @@ def step_time_summary(step_ms):
                 every=[round(x, 3) for x in (step_ms if len(step_ms) <= 40 else step_ms[::max(1, len(step_ms) // 40)])])
 
 
-def timed_steps(G, cfg, z, cond, jitter, steps, warmup, dist_on, telemetry=None, step_ms=None):
-    return timed_loop(lambda: G.forward(z, cond, jitter=jitter, **cfg), steps, warmup, dist_on, telemetry=telemetry,
-                      step_ms=step_ms)
+def timed_steps(G, cfg, z, cond, jitter, steps, warmup, dist_on, telemetry=None, step_ms=None, last=None):
+    """`last` (a dict), when given, receives the output dict of the most recent step under "out"."""
+    def step():
+        out = G.forward(z, cond, jitter=jitter, **cfg)
+        if last is not None:
+            last["out"] = out
+
+    return timed_loop(step, steps, warmup, dist_on, telemetry=telemetry, step_ms=step_ms)
+
+
+def ranked(arrays, rank):
+    """Rank 0 writes <name>.npy, rank r > 0 <name>_rank<r>.npy."""
+    return arrays if rank == 0 else {f"{k}_rank{rank}": v for k, v in arrays.items()}
+
+
+def dump_losses(a, last, rank, world):
+    """--dump-outputs of the training modes: the loss values of the last timed step, float64 scalars."""
+    if getattr(a, "dump_outputs", None):
+        dump_outputs(a.dump_outputs, ranked({k: torch.tensor(float(v), dtype=torch.float64) for k, v in last.items()}, rank),
+                     budget=DUMP_BUDGET_BYTES // world)
 
 
 def discriminator_step_bench(a, rank, world, dist_on, dev):
@@ -153,6 +173,7 @@ def discriminator_step_bench(a, rank, world, dist_on, dev):
                                                 grad_clip=cfg.get("grad_clip", 10.0)))
 
     dt = timed_loop(step, a.steps, a.warmup, dist_on)
+    dump_losses(a, last, rank, world)
     if rank == 0:
         print(json.dumps({
             "metric": "discriminator-step images/sec at 512x256 (G forward + D fwd/bwd + R1)", "value": a.batch * world * a.steps / dt,
@@ -209,6 +230,7 @@ def train_step_bench(a, rank, world, dist_on, dev, emit=True):
 
     dt = timed_loop(step, a.steps, a.warmup, dist_on)
     torch.cuda.synchronize()
+    dump_losses(a, last, rank, world)
     ms = {k: sum(s.elapsed_time(t) for s, t in v[-a.steps:]) / a.steps for k, v in ev.items()}
     line = None
     if rank == 0:
@@ -348,6 +370,60 @@ def load_traffic(workload_key):
     return best, src, busy, when
 
 
+def cgroup_cpus():
+    """CPUs the cgroup's quota allows (cgroup v2 cpu.max, else v1 cpu.cfs_quota_us / cpu.cfs_period_us), or None: no quota."""
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        return None if quota == "max" else max(1, int(quota) // int(period))
+    except (OSError, ValueError):
+        pass
+    try:
+        quota = int(open("/sys/fs/cgroup/cpu/cpu.cfs_quota_us").read())
+        period = int(open("/sys/fs/cgroup/cpu/cpu.cfs_period_us").read())
+        return None if quota <= 0 or period <= 0 else max(1, quota // period)
+    except (OSError, ValueError):
+        return None
+
+
+def host_threads(cap=64):
+    """Threads for the CPU legs: the CPUs this process may actually run on -- its affinity mask, the cgroup's CPU quota
+    when there is one (cgroup_cpus), and OMP_NUM_THREADS when the caller set it -- capped at `cap` (more threads than that only adds
+    contention).  os.cpu_count() alone counts the whole host, and a thread pool sized by it on a quota-limited host mostly waits
+    for its own throttled threads.  Under torchrun OMP_NUM_THREADS is torchrun's default of 1 per rank and is not taken: the
+    CPU legs run on rank 0 alone, after the ranks have finished their collectives."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    quota = cgroup_cpus()
+    if quota is not None:
+        n = min(n, quota)
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0 and "TORCHELASTIC_RUN_ID" not in os.environ:
+        n = min(n, int(omp))
+    return max(1, min(cap, n))
+
+
+DUMP_BUDGET_BYTES = 64_000_000      # --dump-outputs: at most this many bytes of array data in all
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write {name: tensor} as directory/<name>.npy, float64 tensors as float64 and everything else as float32.  When the arrays
+    hold more than `budget` bytes together, each is replaced by the same fixed, seeded sample of its flattened elements (a share
+    of the budget in proportion to its size; the positions depend only on the array's size and `seed`).  -> [paths written]"""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    host = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32) for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in host.values())
+    written = []
+    for name, v in host.items():
+        if total > budget:
+            k = max(1, v.numel() * budget // total - 1)
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(seed))[:k].sort().values
+            v = v.flatten()[idx]
+        path = os.path.join(directory, name + ".npy")
+        np.save(path, v.contiguous().numpy())
+        written.append(path)
+    return written
+
+
 def _cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -382,7 +458,7 @@ def cpu_baseline(cfg, sd, seed=1234, shrink=1, runs=1):
     Bounded sample of the SAME workload: ONE image at FULL size (shrink = 1: the output pixels, rays, samples per ray, widths
     and weights of the timed GPU workload; round 6 -- earlier rounds timed a half-size image and multiplied by four), 1 warm-up
     + `runs` timed runs, median.  `shrink` > 1 (development) times a 1/shrink-size image and scales by shrink^2."""
-    torch.set_num_threads(min(64, os.cpu_count() or 1))      # more threads than this only adds contention
+    torch.set_num_threads(host_threads())
     ocfg = {k: v for k, v in cfg.items() if k != "neural_field_cls"}
     for k in ("gen_height", "gen_width", "render_height", "render_width"):
         ocfg[k] = max(1, cfg[k] // shrink)
@@ -411,7 +487,7 @@ def cpu_baseline_cfg1(runs=1):
     G = gens.Map3DGenerator(**dict(cfg, neural_field_cls=impl.COORDCONCATSIREN)).eval()
     sd = {k: v.detach() for k, v in G.state_dict().items()}
     cfg.pop("neural_field_cls", None)
-    torch.set_num_threads(min(64, os.cpu_count() or 1))
+    torch.set_num_threads(host_threads())
     times = sorted(_oracle_run(cfg, sd, 1, 1234, runs))
     med = times[len(times) // 2]
     return dict(value=1.0 / med, unit="images/s", cores=torch.get_num_threads(), kind="port", runs=[round(t, 2) for t in times],
@@ -433,7 +509,7 @@ def cpu_baseline_cfg2(batch=8, shrink=2, runs=1):
     cfg.pop("neural_field_cls", None)
     for k in ("gen_height", "gen_width", "render_height", "render_width"):
         cfg[k] = max(1, cfg[k] // shrink)
-    torch.set_num_threads(min(64, os.cpu_count() or 1))
+    torch.set_num_threads(host_threads())
     times = sorted(_oracle_run(cfg, sd, batch, 1234, runs))
     med = times[len(times) // 2]
     return dict(value=batch / (med * shrink * shrink), unit="images/s", cores=torch.get_num_threads(), kind="port",
@@ -499,7 +575,7 @@ def self_check(G, cfg, z, cond, jitter, items, frac=0.05, seed=5):
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import h3d_oracle as O
     # torchrun exports OMP_NUM_THREADS=1 to its ranks when N > 1: the oracle leg of rank 0 would run on one thread
-    torch.set_num_threads(min(64, os.cpu_count() or 1))
+    torch.set_num_threads(host_threads())
     out = G.forward(z, cond, jitter=jitter, **cfg)
     rgb, ren = out["rgbs"].cpu(), out["rgbs_render"].cpu()
     sd = {k: v.detach().cpu() for k, v in G.state_dict().items()}
@@ -776,7 +852,7 @@ def compact_line(out):
                     "x2_fallback_items": chk.get("x2_fallback_items")} if chk else None,
         "stage_ms": {k: _r(v, 3) for k, v in list((out.get("stage_ms") or {}).items())[:8]},
         "extra": {k: v for k, v in extra.items() if v is not None},
-        "detail": "bench_detail.json",
+        "detail": out.get("detail", "bench_detail.json"),
     }
     def clip(o, n=400):                              # no string of the line is longer than n characters
         if isinstance(o, dict):
@@ -811,9 +887,9 @@ def write_detail(out, name="bench_detail.json"):
 
 
 def respawn_under_torchrun(a, argv):
-    """`python bench.py --gpus N` with N > 1 and no torchrun environment: re-exec this script as N ranks, one per GPU, the way
+    """`python bench.py --gpus N` with N > 1 and no torchrun environment: run this script again as N ranks, one per GPU, the way
     the driver's contract command does (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
-    --master-port P bench.py ...).  Returns only when no re-exec is needed."""
+    --master-port P bench.py ...), in a child process, and exit with its status.  Returns only when no child is needed."""
     if a.gpus <= 1 or "WORLD_SIZE" in os.environ or "RANK" in os.environ:
         return
     have = torch.cuda.device_count()
@@ -827,7 +903,7 @@ def respawn_under_torchrun(a, argv):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
     sys.stdout.flush()
-    os.execve(sys.executable, cmd, env)
+    raise SystemExit(subprocess.call(cmd, env=env))
 
 
 def check_world(a, world, backend_world=None):
@@ -835,12 +911,17 @@ def check_world(a, world, backend_world=None):
     none)."""
     if world != a.gpus:
         raise SystemExit(f"bench.py: --gpus {a.gpus} but WORLD_SIZE is {world}: launch with --nproc-per-node {a.gpus} "
-                         "(or run `python bench.py --gpus N` without a torchrun environment: it re-executes itself under torchrun)")
+                         "(or run `python bench.py --gpus N` without a torchrun environment: it runs itself under torchrun)")
     if backend_world is not None and backend_world != world:
         raise SystemExit(f"bench.py: process group has {backend_world} ranks, WORLD_SIZE says {world}")
 
 
-def main():
+TRIMS = ("no_cpu", "no_telemetry", "no_extra", "no_check", "check_items")
+
+
+def parse_args(argv=None):
+    """The command line.  --no-cpu / --no-telemetry / --no-extra / --no-check / --check-items trim the --full run; a run given any
+    of them IS a (trimmed) --full run -- stderr says so -- so a caller that asks to trim a leg keeps every leg it did not trim."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -856,13 +937,40 @@ def main():
     ap.add_argument("--amp", default="none", choices=["none", "fp16", "bf16"],
                     help="trainstep: autocast type of the library GEMMs / convolutions (the reference's AMP mode is fp16; bf16 "
                          "is there for measurement only: too coarse for the sine layers, and MIOpen's bf16 convolutions are slow)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-telemetry", action="store_true", help="do not sample clocks / power around the timed region")
-    ap.add_argument("--no-extra", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the oracle-subset self-check of the timed workload")
-    ap.add_argument("--check-items", type=int, default=0, help="self-check only the first N items of the batch (0: all; development)")
-    a = ap.parse_args()
-    respawn_under_torchrun(a, sys.argv[1:])
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines (implies --full)")
+    ap.add_argument("--no-telemetry", action="store_true", help="--full without sampling clocks / power around the timed region "
+                                                                "(implies --full)")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the side workloads (implies --full)")
+    ap.add_argument("--no-check", action="store_true", help="--full without the oracle-subset self-check of the timed workload "
+                                                            "(implies --full)")
+    ap.add_argument("--check-items", type=int, default=0, help="--full, self-checking only the first N items of the batch (0: all; "
+                                                               "development; implies --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: per-stage times, clocks / power, kernel "
+                         "rooflines, the other configurations and engines, config 4's training iteration, the oracle self-check, "
+                         "the CPU baselines, and the full record in bench_detail.json (the --no-* options trim this)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; a fixed "
+                         "seeded sample of each array when all of them together exceed 64 MB)")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    trims = [t for t in TRIMS if getattr(a, t)]
+    if trims and not a.full:
+        a.full = True
+        print("bench.py: " + ", ".join("--" + t.replace("_", "-") for t in trims) + " trim(s) the --full run: running with --full",
+              file=sys.stderr)
+    return a
+
+
+def plain_line(head):
+    """The result line of a run without --full: the headline keys of `head`, the side legs null (none of them ran)."""
+    return compact_line(dict(head, roofline=None, cpu_baseline=None, checked=None, detail=None))
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    respawn_under_torchrun(a, sys.argv[1:] if argv is None else list(argv))
 
     rank, world, local, dist_on = dist_env()
     check_world(a, world)
@@ -888,21 +996,28 @@ def main():
     render = tuple(int(v) for v in a.render.split("x")) if a.render else (H * 3 // 16, W * 3 // 16)
     G, cfg = build_generator(a.config, (H, W), render, a.samples, dev)
     z, cond, jitter = make_inputs(cfg, a.batch, dev, seed=1234 + rank)
-    G.stage_timer = StageTimer()
-    tel = None
-    if rank == 0 and not a.no_telemetry:
-        tel = importlib.import_module("3dhumangan_amd._telemetry").Telemetry(local)
-    step_ms = []
-    dt = timed_steps(G, cfg, z, cond, jitter, a.steps, a.warmup, dist_on, telemetry=tel, step_ms=step_ms)
+    # a plain run times the steps and nothing else; per-stage events, per-step events and the telemetry thread only with --full
+    tel, step_ms = None, None
+    if a.full:
+        G.stage_timer = StageTimer()
+        if rank == 0 and not a.no_telemetry:
+            tel = importlib.import_module("3dhumangan_amd._telemetry").Telemetry(local)
+        step_ms = []
+    last = {}
+    dt = timed_steps(G, cfg, z, cond, jitter, a.steps, a.warmup, dist_on, telemetry=tel, step_ms=step_ms, last=last)
     torch.cuda.synchronize()
     # drop warm-up samples: keep the last `steps` events of each stage
     stage_ms = {}
-    for k, ev in G.stage_timer.events.items():
-        ev = ev[-a.steps:]
-        stage_ms[k] = (sum(x.elapsed_time(y) for x, y in ev) / len(ev), len(ev))
-    G.stage_timer = None
+    if a.full:
+        for k, ev in G.stage_timer.events.items():
+            ev = ev[-a.steps:]
+            stage_ms[k] = (sum(x.elapsed_time(y) for x, y in ev) / len(ev), len(ev))
+        G.stage_timer = None
     n_images = a.batch * world * a.steps
     value = n_images / dt
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, ranked(last["out"], rank), budget=DUMP_BUDGET_BYTES // world)
+    last.clear()
 
     # every collective of the run is behind us (the MAX over ranks of the elapsed time): ALL ranks leave the process group here,
     # together -- rank 0 then spends a minute on single-rank legs (roofline of A6, the oracle check) and must not find itself
@@ -912,6 +1027,25 @@ def main():
         torch.distributed.destroy_process_group()
         dist_on = False
     if rank != 0:
+        return
+
+    head = {
+        "metric": "generator images/sec at 512^2", "value": value, "unit": "images/s", "n_gpus": world,
+        "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None,
+        "dtype": f"f32 in/out, f32 accumulate; contractions field {G.neural_field.precision} / synthesis "
+                 f"{G.synthesis_plan(dev).engine} (x2 = f16 product + block-scaled fp6 cross terms, x3 = three f16/bf16 products)",
+        "data": "synthetic",
+        "config": {"workload": f"BASELINE cfg 3: {a.config} generator-only forward, {H}x{W} out, {render[0]}x{render[1]} rays x "
+                               f"{a.samples} samples, hidden {cfg['hidden_dim']}, batch {a.batch}/GPU, {cfg['map3d_mode']}, random-init "
+                               "weights, procedural SMPL-like pose" if (a.config, H, W, a.samples, a.batch) == ("MAP3DBN512", 512, 512, 64, 16)
+                               else f"{a.config} generator-only forward, {H}x{W} out, {render[0]}x{render[1]} rays x {a.samples} samples, "
+                                    f"hidden {cfg['hidden_dim']}, batch {a.batch}/GPU, {cfg['map3d_mode']}",
+                   "global_batch": a.batch * world, "parallelism": f"batch-sharded replicas x{world} (no collective)"},
+    }
+    if not a.full:
+        sys.stdout.flush()
+        print(plain_line(head), flush=True)
         return
 
     kernels = kernel_rooflines(G, cfg, a.batch, stage_ms)
@@ -987,19 +1121,7 @@ def main():
             extra.setdefault("cfg4_trainstep_b4", dict(error=repr(e)[:300]))
             extra["cfg4_trainstep_error"] = repr(e)[:300]
 
-    out = {
-        "metric": "generator images/sec at 512^2", "value": value, "unit": "images/s", "n_gpus": world,
-        "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None,
-        "dtype": f"f32 in/out, f32 accumulate; contractions field {G.neural_field.precision} / synthesis "
-                 f"{G.synthesis_plan(dev).engine} (x2 = f16 product + block-scaled fp6 cross terms, x3 = three f16/bf16 products)",
-        "data": "synthetic",
-        "config": {"workload": f"BASELINE cfg 3: {a.config} generator-only forward, {H}x{W} out, {render[0]}x{render[1]} rays x "
-                               f"{a.samples} samples, hidden {cfg['hidden_dim']}, batch {a.batch}/GPU, {cfg['map3d_mode']}, random-init "
-                               "weights, procedural SMPL-like pose" if (a.config, H, W, a.samples, a.batch) == ("MAP3DBN512", 512, 512, 64, 16)
-                               else f"{a.config} generator-only forward, {H}x{W} out, {render[0]}x{render[1]} rays x {a.samples} samples, "
-                                    f"hidden {cfg['hidden_dim']}, batch {a.batch}/GPU, {cfg['map3d_mode']}",
-                   "global_batch": a.batch * world, "parallelism": f"batch-sharded replicas x{world} (no collective)"},
+    out = dict(head, **{
         "roofline": roof,
         "roofline_hbm_kernel": dict(kernel="h3d_ray_integrate", **{k: kernels["h3d_ray_integrate"][k] for k in
                                     ("bound", "achieved", "peak", "unit", "frac", "traffic")}),
@@ -1008,7 +1130,7 @@ def main():
         "step_ms": step_time_summary(step_ms),
         "telemetry": tel.report() if tel is not None else None,
         "extra": extra,
-    }
+    })
     # energy per image of THIS rank's GPU over the timed region: median sampled socket power x elapsed time / its images
     try:
         pw = out["telemetry"]["timed"]["socket_power_W"]["median"]

@@ -1,6 +1,6 @@
 """The ONE stdout line of bench.py is what the driver parses (round 4's 25.6 KB line came back `parsed: null`): it must be a
 single line, strict JSON (no NaN / Infinity), under 4 KB, carry the contract keys with `roofline` and `cpu_baseline`, and hold no
-array longer than 16.  Also: `--gpus N` without a torchrun environment re-executes the script under torch.distributed.run, and
+array longer than 16.  Also: `--gpus N` without a torchrun environment runs the script under torch.distributed.run, and
 a world size that disagrees with `--gpus` fails loudly."""
 import argparse
 import json
@@ -129,7 +129,7 @@ def test_detail_file_is_strict_json(tmp_path, monkeypatch):
 
 def test_gpus_n_respawns_under_torchrun(monkeypatch):
     calls = []
-    monkeypatch.setattr(os, "execve", lambda exe, cmd, env: calls.append((exe, cmd, env)))
+    monkeypatch.setattr(bench.subprocess, "call", lambda cmd, env: calls.append((cmd[0], cmd, env)) or 3)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TORCHELASTIC_RUN_ID"):
         monkeypatch.delenv(k, raising=False)
     bench.respawn_under_torchrun(argparse.Namespace(gpus=1), ["--gpus", "1"])
@@ -140,7 +140,9 @@ def test_gpus_n_respawns_under_torchrun(monkeypatch):
         bench.respawn_under_torchrun(argparse.Namespace(gpus=8), ["--gpus", "8"])       # fewer GPUs than asked for: say so, do not spawn
     assert calls == []
     monkeypatch.setattr(torch.cuda, "device_count", lambda: 8)
-    bench.respawn_under_torchrun(argparse.Namespace(gpus=8), ["--gpus", "8", "--steps", "20", "--warmup", "5"])
+    with pytest.raises(SystemExit) as ex:                       # a child process runs the ranks; its status is the exit status
+        bench.respawn_under_torchrun(argparse.Namespace(gpus=8), ["--gpus", "8", "--steps", "20", "--warmup", "5"])
+    assert ex.value.code == 3
     (exe, cmd, env), = calls
     assert exe == sys.executable and cmd[:3] == [sys.executable, "-m", "torch.distributed.run"]
     assert "--nproc-per-node=8" in cmd and "--nnodes=1" in cmd
@@ -195,3 +197,122 @@ def test_check_cells_cover_five_percent_and_the_brightest_pixels():
     small = dict(gen_height=16, gen_width=8, render_height=8, render_width=4)
     cells, K = bench.check_cells(small, 0, 0.05, 5)
     assert all(0 <= cy < 8 and 0 <= cx < 4 for cy, cx in cells) and K >= 1
+
+
+def _fake_run(monkeypatch, tmp_path):
+    """bench.main() on the CPU: the generator, its inputs and the timed loop are stand-ins, every side leg raises if it is
+    called.  -> the list the stand-in timed loop appends its keyword arguments to."""
+    import types
+    import torch
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TORCHELASTIC_RUN_ID"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("MIOPEN_USER_DB_PATH", str(tmp_path))
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *x: None)
+    plan = types.SimpleNamespace(engine="f16x2")
+    G = types.SimpleNamespace(neural_field=types.SimpleNamespace(precision="f16x2"), synthesis_plan=lambda dev: plan)
+    cfg = {"hidden_dim": 256, "map3d_mode": "mixed"}
+    monkeypatch.setattr(bench, "build_generator", lambda *x: (G, cfg))
+    monkeypatch.setattr(bench, "make_inputs", lambda *x, **k: (None, None, None))
+    calls = []
+
+    def timed_steps(G_, cfg_, z, cond, jitter, steps, warmup, dist_on, telemetry=None, step_ms=None, last=None):
+        calls.append(dict(steps=steps, warmup=warmup, telemetry=telemetry, step_ms=step_ms))
+        last["out"] = {"rgbs": torch.full((2, 3, 4, 4), 0.5), "rgbs_render": torch.ones(2, 3, 2, 2)}
+        return 0.25 * steps
+
+    monkeypatch.setattr(bench, "timed_steps", timed_steps)
+
+    class SideLeg(Exception):
+        pass
+
+    def side(*x, **k):
+        raise SideLeg()
+
+    for name in ("kernel_rooflines", "ray_integrate_roofline", "self_check", "cpu_baseline", "write_detail", "op_rooflines"):
+        monkeypatch.setattr(bench, name, side)
+    return calls, SideLeg
+
+
+def test_plain_line_carries_the_headline_and_no_side_legs(monkeypatch, tmp_path, capsys):
+    """A run without --full: exactly --steps timed steps with no per-step events or telemetry, the last step's outputs in
+    --dump-outputs, one line with the headline keys and the side legs null -- and none of the side legs called."""
+    import numpy as np
+    calls, _ = _fake_run(monkeypatch, tmp_path)
+    bench.main(["--gpus", "1", "--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path / "dump")])
+    assert calls == [dict(steps=4, warmup=2, telemetry=None, step_ms=None)]
+    lines = capsys.readouterr().out.strip().split("\n")
+    assert len(lines) == 1
+    line = _strict_loads(lines[0])
+    assert all(k in line for k in CONTRACT)
+    assert line["ms_per_step"] == pytest.approx(250.0) and line["value"] == pytest.approx(16 * 4 / 1.0)
+    assert line["unit"] == "images/s" and line["higher_is_better"] is True and "f16x2" in line["dtype"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["checked"] is None
+    assert line["extra"] == {} and line["stage_ms"] == {} and line["detail"] is None
+    assert np.array_equal(np.load(tmp_path / "dump" / "rgbs.npy"), np.full((2, 3, 4, 4), 0.5, np.float32))
+    assert np.load(tmp_path / "dump" / "rgbs_render.npy").shape == (2, 3, 2, 2)
+    assert not (tmp_path / "bench_detail.json").exists()
+
+
+@pytest.mark.parametrize("argv", [["--full"], ["--no-cpu", "--no-extra", "--no-check"], ["--check-items", "2"]])
+def test_full_and_trimmed_runs_reach_the_side_legs(monkeypatch, tmp_path, argv):
+    """--full, and any option that trims the full run (a trimmed --full run), go on to the roofline legs after the timed steps."""
+    calls, SideLeg = _fake_run(monkeypatch, tmp_path)
+    with pytest.raises(SideLeg):
+        bench.main(["--steps", "3", "--warmup", "1", "--no-telemetry"] + argv)
+    assert len(calls) == 1 and calls[0]["step_ms"] == []
+
+
+def test_parse_args_full_only_when_asked_or_trimmed():
+    assert bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"]).full is False
+    assert bench.parse_args(["--full"]).full is True
+    for trim in (["--no-cpu"], ["--no-extra"], ["--no-check"], ["--no-telemetry"], ["--check-items", "3"]):
+        assert bench.parse_args(trim).full is True, trim
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_writes_float_arrays_whole_or_as_a_fixed_sample(tmp_path):
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    arrays = {"rgbs": torch.randn(2, 3, 8, 8, generator=g), "rgbs_render": torch.randn(2, 3, 4, 4, generator=g).half(),
+              "loss": torch.tensor(0.25, dtype=torch.float64)}
+    written = bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert sorted(os.path.basename(p) for p in written) == ["loss.npy", "rgbs.npy", "rgbs_render.npy"]
+    rgbs, ren, loss = (np.load(tmp_path / "whole" / f"{n}.npy") for n in ("rgbs", "rgbs_render", "loss"))
+    assert rgbs.dtype == np.float32 and np.array_equal(rgbs, arrays["rgbs"].numpy())
+    assert ren.dtype == np.float32 and np.array_equal(ren, arrays["rgbs_render"].float().numpy())
+    assert loss.dtype == np.float64 and float(loss) == 0.25
+    # over the budget: every array shrinks to the same seeded sample of its elements, within the budget in all
+    budget = 256
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget=budget)
+    total = 0
+    for n in arrays:
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert np.array_equal(a, b) and a.ndim == 1 and a.size >= 1
+        assert np.isin(a, arrays[n].float().numpy().ravel()).all()
+        total += a.nbytes
+    assert total <= budget
+
+
+def test_host_threads_stays_within_the_cpus_of_the_process(monkeypatch):
+    for k in ("OMP_NUM_THREADS", "TORCHELASTIC_RUN_ID"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(bench, "cgroup_cpus", lambda: None)
+    n = bench.host_threads()
+    assert 1 <= n <= 64 and n == min(64, len(os.sched_getaffinity(0)))
+    assert bench.host_threads(cap=1) == 1
+    monkeypatch.setattr(os, "sched_getaffinity", lambda pid: set(range(128)))
+    assert bench.host_threads() == 64                                   # capped
+    monkeypatch.setattr(bench, "cgroup_cpus", lambda: 16)
+    assert bench.host_threads() == 16                                   # the cgroup's quota
+    monkeypatch.setenv("OMP_NUM_THREADS", "3")
+    assert bench.host_threads() == 3                                    # the caller's setting
+    monkeypatch.setenv("TORCHELASTIC_RUN_ID", "x")
+    assert bench.host_threads() == 16                                   # torchrun's per-rank default of 1 is not taken
+    monkeypatch.setenv("OMP_NUM_THREADS", "garbage")
+    monkeypatch.delenv("TORCHELASTIC_RUN_ID")
+    assert bench.host_threads() == 16

@@ -7,20 +7,20 @@ OUT=$PWD/gpurun_out/$R
 mkdir -p $OUT
 REPO=$PWD
 KERN='x3_kernel|x3t_kernel|geo_features|mesh_sort|ray_integrate|conv_x3|wgrad|synthesis_check'
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err        # the driver's protocol
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err        # the contract command + every side leg
 cp bench_detail.json $OUT/bench_detail.json                                              # the full record behind the compact line
-python bench.py --steps 200 --warmup 5 --no-extra --no-cpu --no-check > $OUT/bench_200steps.json 2>> $OUT/bench.err
+python bench.py --full --steps 200 --warmup 5 --no-extra --no-cpu --no-check > $OUT/bench_200steps.json 2>> $OUT/bench.err
 cp bench_detail.json $OUT/bench_200steps_detail.json
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/stats -o k -- python $REPO/bench.py --steps 20 --warmup 5 --no-cpu --no-extra --no-check > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/stats -o k -- python $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu --no-extra --no-check > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 600 rocprofv3 --pmc $c -d $OUT/pmc_$c -o p -- python $REPO/bench.py --no-cpu --no-extra --no-check --steps 2 --warmup 1 > /dev/null 2> $OUT/pmc_$c.err
+  timeout 600 rocprofv3 --pmc $c -d $OUT/pmc_$c -o p -- python $REPO/bench.py --full --no-cpu --no-extra --no-check --steps 2 --warmup 1 > /dev/null 2> $OUT/pmc_$c.err
 done
-timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_LDS -d $OUT/pmc_sq1 -o p -- python $REPO/bench.py --no-cpu --no-extra --no-check --steps 2 --warmup 1 > /dev/null 2> $OUT/pmc_sq1.err
-timeout 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT -d $OUT/pmc_sq2 -o p -- python $REPO/bench.py --no-cpu --no-extra --no-check --steps 2 --warmup 1 > /dev/null 2> $OUT/pmc_sq2.err
+timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_LDS -d $OUT/pmc_sq1 -o p -- python $REPO/bench.py --full --no-cpu --no-extra --no-check --steps 2 --warmup 1 > /dev/null 2> $OUT/pmc_sq1.err
+timeout 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT -d $OUT/pmc_sq2 -o p -- python $REPO/bench.py --full --no-cpu --no-extra --no-check --steps 2 --warmup 1 > /dev/null 2> $OUT/pmc_sq2.err
 # the wide workload (MAP3DBN512L, hidden 420: the x3t engines)
-timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/stats_wide -o k -- python $REPO/bench.py --config MAP3DBN512L --no-cpu --no-extra --no-check --steps 5 > $OUT/bench_wide_under_rocprof.json 2> $OUT/stats_wide.err
-timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA -d $OUT/pmc_wide -o p -- python $REPO/bench.py --config MAP3DBN512L --no-cpu --no-extra --no-check --steps 2 --warmup 1 > /dev/null 2> $OUT/pmc_wide.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/stats_wide -o k -- python $REPO/bench.py --full --config MAP3DBN512L --no-cpu --no-extra --no-check --steps 5 > $OUT/bench_wide_under_rocprof.json 2> $OUT/stats_wide.err
+timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA -d $OUT/pmc_wide -o p -- python $REPO/bench.py --full --config MAP3DBN512L --no-cpu --no-extra --no-check --steps 2 --warmup 1 > /dev/null 2> $OUT/pmc_wide.err
 cd $REPO
 python tools/rocprof_summary.py $(find $OUT/stats -name '*.db' | head -1) $OUT/kernel_stats.csv
 python tools/rocprof_summary.py $(find $OUT/stats_wide -name '*.db' | head -1) $OUT/wide_kernel_stats.csv

@@ -22,11 +22,11 @@ done; done
 timeout 900 python -m pytest tests -x -q -m gpu -p no:cacheprovider > $OUT/gpu_suite.log 2>&1
 echo "suite rc=$?" >> $OUT/gpu_suite.log
 tail -3 $OUT/gpu_suite.log
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 cp bench_detail.json $OUT/bench_detail.json
 tail -c 600 $OUT/bench.json
 cd /tmp
-timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/stats -o k -- python $REPO/bench.py --steps 20 --warmup 5 --no-cpu --no-extra --no-check > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
+timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/stats -o k -- python $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu --no-extra --no-check > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 cd $REPO
 python tools/rocprof_summary.py $(find $OUT/stats -name '*.db' | head -1) $OUT/kernel_stats.csv
 find $OUT -name '*.db' -delete

@@ -9,10 +9,10 @@ OUT=$PWD/gpurun_out/$R
 mkdir -p $OUT
 REPO=$PWD
 KERN='x3_kernel|x3t_kernel|geo_features|mesh_sort|ray_integrate|conv_x3|wgrad|synthesis_check'
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err        # the driver's protocol
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err        # the contract command + every side leg
 cp bench_detail.json $OUT/bench_detail.json
 cd /tmp && export TMPDIR=/tmp
-B="python $REPO/bench.py --no-cpu --no-extra --no-check"
+B="python $REPO/bench.py --full --no-cpu --no-extra --no-check"
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/stats -o k -- $B --steps 20 --warmup 5 > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 600 rocprofv3 --pmc $c -d $OUT/pmc_$c -o p -- $B --steps 2 --warmup 1 > /dev/null 2> $OUT/pmc_$c.err
@@ -40,7 +40,7 @@ cd $REPO
 python tools/rocprof_summary.py $(find $OUT/stats_train -name '*.db' | head -1) $OUT/trainstep_kernel_stats.csv
 python tools/rocprof_summary.py $(find $OUT/stats_train_amp -name '*.db' | head -1) $OUT/trainstep_amp_fp16_kernel_stats.csv
 # one-rank RCCL lines: the driver's N > 1 command line with one rank (process group over RCCL, barrier, MAX all-reduce of the time)
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 10 --warmup 3 --no-extra --no-cpu --check-items 2 > $OUT/bench_torchrun_1rank_rccl.json 2> $OUT/torchrun.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --steps 10 --warmup 3 --no-extra --no-cpu --check-items 2 > $OUT/bench_torchrun_1rank_rccl.json 2> $OUT/torchrun.err
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 1 --mode trainstep --batch 4 --steps 3 --warmup 2 > $OUT/trainstep_torchrun_1rank_rccl.json 2>> $OUT/torchrun.err
 find $OUT -name '*.db' -delete
 tail -c 600 $OUT/bench.json; echo; tail -c 300 $OUT/bench_torchrun_1rank_rccl.json; echo; tail -c 300 $OUT/trainstep_torchrun_1rank_rccl.json

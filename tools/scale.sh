@@ -13,9 +13,9 @@ for N in 1 2 4 8; do
   PORT=$((29500 + N))
   for MODE in generator trainstep; do
     EXTRA="--no-cpu --no-extra"; [ "$MODE" = trainstep ] && EXTRA="--batch 4"
-    # bench.py re-executes itself under torch.distributed.run for N > 1 (one rank per GPU); its last stdout line is the compact
-    # contract line (< 4 KB), the full record goes to bench_detail.json
-    python bench.py --gpus "$N" --steps "$STEPS" --warmup "$WARM" --mode $MODE $EXTRA > "$OUT/${MODE}_n$N.json" 2> "$OUT/${MODE}_n$N.err"
+    # bench.py runs itself under torch.distributed.run for N > 1 (one rank per GPU); its last stdout line is the compact
+    # contract line (< 4 KB); with --full the full record goes to bench_detail.json
+    python bench.py --full --gpus "$N" --steps "$STEPS" --warmup "$WARM" --mode $MODE $EXTRA > "$OUT/${MODE}_n$N.json" 2> "$OUT/${MODE}_n$N.err"
     [ -f bench_detail.json ] && [ "$MODE" = generator ] && cp bench_detail.json "$OUT/${MODE}_n${N}_detail.json"
     tail -n 1 "$OUT/${MODE}_n$N.json" | cut -c 1-400; echo
   done
