@@ -148,6 +148,8 @@ _SIGNATURES = {
     "h3d_bn_bwd_finish": (C.c_int, [_p] * 7 + [_i, _p]),
     "h3d_bias_act": (C.c_int, [_p, _p, _p, _l, _i, _l, _l, _i, _f, _f, _f, _p]),
     "h3d_bias_act_grad": (C.c_int, [_p, _p, _p, _p, _p, _p, _l, _i, _l, _l, _i, _i, _f, _f, _f, _p]),
+    "h3d_mesh_raster_bytes": (C.c_int64, [_i, _i]),
+    "h3d_mesh_rasterize": (C.c_int, [_p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "h3d_upfirdn2d": (C.c_int, [_p, _p, _p, _i, _i, _i, _i, _i, C.POINTER(_l), _i, _i, _i, _i, C.POINTER(_l),
                                 _i, _i, _i, _i, _i, _i, _i, _f, _p]),
 }

@@ -4,7 +4,10 @@ convention (:26-29), angle schedule (:35-43), uint8 conversion (:59-62) and outp
 
 The SMPL model file and the SHHQ dataset cannot ship, so `--synthetic-conditions` (the default when --dataroot is
 absent) drives the generator with the procedural body of `synthetic.py`; with random-init weights (no
-`--checkpoint`) it is a plumbing / throughput run.
+`--checkpoint`) it is a plumbing / throughput run.  `--smpl-record PATH.npz` drives it through the real front-end
+instead: one SMPL regression record (the keys preprocess_smpl_fix_body reads) with `joints_index`,
+`smpl_tpose_vertices`, `faces` and `faces_to_labels`; the camera preprocessor then rasterises the mesh on the device
+and the `_smpl` images are its semantics.
 
     python -m 3dhumangan_amd.apps.sample_from_generator --config MAP3DBN --seeds 1 2 --n_angles 8 --save png
 """
@@ -16,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import checkpoints, configs, synthetic
+from ..lib import data as lib_data
 from ..lib import generators as lib_generators
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -65,6 +69,17 @@ def generate_frames(generator, preprocessor, config, seed, conditions, n_angles,
     return to_uint8_nhwc(torch.cat(frames).float()), to_uint8_nhwc(torch.cat(semantics).float())
 
 
+def load_smpl_record(path, dev):
+    """--smpl-record: -> (batch-1 conditions on `dev`, a CameraPreprocessor on `dev` with the record's faces and labels)."""
+    rec = dict(np.load(path))
+    cond = lib_data.preprocess_smpl_fix_body(rec, rec["joints_index"].tolist(), rec["smpl_tpose_vertices"])
+    cond = {k: v[None].to(dev) for k, v in cond.items()}
+    cond["scales"] = cond["scales"].reshape(1)
+    pre = lib_data.CameraPreprocessor(dev)
+    pre.init_smpl(torch.as_tensor(rec["faces"]), torch.as_tensor(rec["faces_to_labels"]))
+    return cond, pre
+
+
 def _save(path_stem, frames, mode):
     from PIL import Image
     if mode == "png":
@@ -101,6 +116,8 @@ def main(argv=None):
     ap.add_argument("--save", type=str, default="png", choices=["mp4", "png", "gif"])
     ap.add_argument("--stitch", default=False, action="store_true")
     ap.add_argument("--synthetic-conditions", action="store_true", default=True)
+    ap.add_argument("--smpl-record", type=str, default=None, help="an .npz SMPL record (+ joints_index, smpl_tpose_vertices, "
+                    "faces, faces_to_labels): conditions and the _smpl images through the front-end and its rasteriser")
     opt = ap.parse_args(argv)
     if opt.dataroot is not None:
         raise NotImplementedError("the SHHQ dataset reader / SMPL preprocessor need licensed assets and pytorch3d; "
@@ -125,8 +142,10 @@ def main(argv=None):
     generator.set_device(device)
     generator.eval()
     preprocessor = synthetic.SyntheticPreprocessor(device)
+    if opt.smpl_record is not None:
+        record, preprocessor = load_smpl_record(opt.smpl_record, device)
     for seed in opt.seeds:
-        data = synthetic.make_conditions(1, 6890, seed=seed)
+        data = record if opt.smpl_record is not None else synthetic.make_conditions(1, 6890, seed=seed)
         frames, semantics = generate_frames(generator, preprocessor, config, seed, data, opt.n_angles, math.pi / 6, 0,
                                             opt.back_and_forth)
         if opt.stitch:

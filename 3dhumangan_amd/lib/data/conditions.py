@@ -5,17 +5,21 @@
   CameraPreprocessor         the camera matrices for a requested view (reference: SHHQPreprocessor.forward /
                              forward_with_rotation / _forward_fix_body, lib/data/preprocessor.py:45-97)
 
-Both are pinned to the reference's own methods by tests/golden/frontend.npz.  Not reproduced: the pytorch3d mesh rasteriser
-of the preprocessor (:138-176; it only feeds the discriminator's conditioning and the app's side-by-side view) --
-`rasterized_semantics` comes back as an all-zero map.  Third-party boundary: pytorch3d.transforms.euler_angles_to_matrix
+Both are pinned to the reference's own methods by tests/golden/frontend.npz.  The preprocessor's mesh rasteriser (:138-176,
+pytorch3d in the reference) runs on the HIP kernel of lib/components/raster.py once `init_smpl` has handed it the SMPL faces and
+their part labels: forward_with_rotation then returns `rasterized_segments` (the segmentation target of the trainer) and the real
+`rasterized_semantics`; without `init_smpl` the semantics are an all-zero map and there are no segments.  Third-party boundary: pytorch3d.transforms.euler_angles_to_matrix
 (pinned 0.6.2, not installed): euler_xyz_to_matrix follows its published definition, Rx(a) @ Ry(b) @ Rz(c) for "XYZ".
 """
 import math
 
 import torch
 
+from ..components import raster
+
 FOV = math.pi * 12 / 180
 FOCAL = 1.0 / math.tan(FOV / 2)                      # 9.5144: intrinsics[0,0] of every sample
+FOCAL_RASTER = 1.0 / math.tan(math.pi / 360)         # 114.59: the rasteriser's 1-degree camera (preprocessor.py:145-146)
 
 
 def euler_xyz_to_matrix(euler):
@@ -66,6 +70,15 @@ def preprocess_smpl_fix_body(pred, joints_index, smpl_tpose_vertices, inference=
     return out
 
 
+def raster_translation(data):
+    """T of the rasteriser's camera, [B,3] (preprocessor.py:147-148): the record's x/y offsets, depth f_r / (2 scales).  With
+    R = data["raster_rotation"] and focal -f_r the mesh lands where the generator's camera sees it (the 0.5 assumes H = 2 W, the
+    shape of every shipped config)."""
+    T_raster = data["T"][:, :3, -1].clone()
+    T_raster[:, -1] = FOCAL_RASTER / data["scales"].reshape(-1) * 0.5
+    return T_raster
+
+
 class CameraPreprocessor:
     """coordinate_mode "fix_body": world2cam = R @ T @ [root_rotation @ Rx(pi - v) Ry(-h) Rz(-r)], cam2world its inverse.
     Same call surface as the reference's SHHQPreprocessor (forward / forward_with_rotation / to)."""
@@ -74,6 +87,17 @@ class CameraPreprocessor:
         self.device = device
         if kwargs.get("coordinate_mode", "fix_body") != "fix_body":
             raise NotImplementedError("only coordinate_mode='fix_body' (every shipped config) is provided")
+        self.smpl_faces = None
+        self.smpl_faces_to_labels = None
+
+    @torch.no_grad()
+    def init_smpl(self, smpl_faces, smpl_faces_to_labels):
+        """The SMPL topology [F,3] and the per-face part labels [F] (preprocessor.py:38-42); enables the rasteriser."""
+        self.smpl_faces = torch.as_tensor(smpl_faces).long().clone()
+        self.smpl_faces_to_labels = torch.as_tensor(smpl_faces_to_labels).long().clone()
+        if self.smpl_faces.dim() != 2 or self.smpl_faces.shape[1] != 3 or self.smpl_faces_to_labels.shape != self.smpl_faces.shape[:1]:
+            raise ValueError(f"init_smpl: faces [F,3] and labels [F] expected, got {tuple(self.smpl_faces.shape)}, "
+                             f"{tuple(self.smpl_faces_to_labels.shape)}")
 
     def to(self, device):
         self.device = device
@@ -107,5 +131,18 @@ class CameraPreprocessor:
         data["cam2world_matrices"] = torch.inverse(world2cam.float())
         data["raster_rotation"] = torch.inverse(R)                  # R_raster of the reference (feeds its rasteriser)
         h, w = kwargs.get("gen_height", 1), kwargs.get("gen_width", 1)
-        data["rasterized_semantics"] = torch.zeros(B, 3, h, w, device=dev)
+        if self.smpl_faces is None:
+            data["rasterized_semantics"] = torch.zeros(B, 3, h, w, device=dev)
+            return data
+        return self._forward_rasterize(data, data["raster_rotation"], h, w)
+
+    def _forward_rasterize(self, data, R_raster, h, w):
+        """preprocessor.py:138-176: the posed SMPL mesh at the sampled view, a 1-degree camera at distance f_r / (2 scales)."""
+        dev = data["scales"].device
+        T_raster = raster_translation(data)
+        faces, labels = self.smpl_faces.to(dev), self.smpl_faces_to_labels.to(dev)
+        seg, sem = raster.rasterize_segments_semantics(data["vertices"], faces, R_raster, T_raster, -FOCAL_RASTER, (h, w), labels,
+                                                       data["tpose_vertices"][0])
+        data["rasterized_semantics"] = sem
+        data["rasterized_segments"] = seg
         return data

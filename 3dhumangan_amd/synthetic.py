@@ -145,3 +145,113 @@ def make_conditions(batch, n_vertices=6890, seed=0, pose_scale=0.5, scale=0.8, h
 
 # The camera front-end lives in lib/data/conditions.py (pinned to the reference's preprocessor); the old names stay importable.
 from .lib.data.conditions import CameraPreprocessor as SyntheticPreprocessor, euler_xyz_to_matrix  # noqa: E402,F401
+
+
+# --- a triangulated stand-in for the SMPL mesh (the rasteriser's input) -----------------------------------------------------
+
+TUBE_SEGMENTS = 12          # vertices per ring
+TUBE_RINGS = 574            # rings over the 24 bones: 24 * 574 = 13 776 faces (SMPL's count), 12 * 574 + 48 = 6 936 vertices
+
+
+def tube_body():
+    """A closed triangulated tube around each of the 24 bones of `template_body` (bone j runs from its parent joint to joint j;
+    the root's is a 0.10 stub upwards), capped by a pole at each end.  -> rest joints [24,3], rest vertices [V,3], LBS weights
+    [V,24] (the same rule as template_body: softmax over the 4 nearest joints), faces int64 [F,3], per-face part labels int64
+    [F] (the bone index 0..23).  F = 13 776 and V = 6 936: SMPL-sized, deterministic, no licensed asset."""
+    J = torch.tensor(_REST, dtype=torch.float64)
+    rad = torch.tensor(_RADIUS, dtype=torch.float64)
+    par = [max(p, 0) for p in PARENTS]
+    blen = (J - J[par]).norm(dim=-1)
+    blen[0] = 0.10
+    rings = (blen / blen.sum() * (TUBE_RINGS - 3 * 24)).floor().long() + 3
+    order = torch.argsort(blen, descending=True)
+    for i in range(TUBE_RINGS - int(rings.sum())):
+        rings[order[i % 24]] += 1
+    k = TUBE_SEGMENTS
+    ang = torch.arange(k, dtype=torch.float64) * (2 * math.pi / k)
+    verts, faces, labels = [], [], []
+    n_v = 0
+    for j in range(24):
+        a = J[par[j]]
+        axis = J[j] - a if j > 0 else torch.tensor([0.0, 0.10, 0.0], dtype=torch.float64)
+        axis_n = axis / axis.norm()
+        helper = torch.tensor([0.0, 1.0, 0.0] if abs(float(axis_n[1])) < 0.9 else [1.0, 0.0, 0.0], dtype=torch.float64)
+        u = torch.linalg.cross(axis_n, helper)
+        u = u / u.norm()
+        w = torch.linalg.cross(axis_n, u)
+        n = int(rings[j])
+        t = torch.linspace(0, 1, n, dtype=torch.float64)
+        ring = a + t[:, None, None] * axis + rad[j] * (torch.cos(ang)[None, :, None] * u + torch.sin(ang)[None, :, None] * w)
+        poles = torch.stack([a - 0.5 * rad[j] * axis_n, a + axis + 0.5 * rad[j] * axis_n])
+        verts += [ring.reshape(-1, 3), poles]
+        idx = lambda i, m: n_v + i * k + (m % k)                                          # noqa: E731
+        pa, pb = n_v + n * k, n_v + n * k + 1
+        tri = []
+        for i in range(n - 1):
+            for m in range(k):
+                tri += [(idx(i, m), idx(i, m + 1), idx(i + 1, m + 1)), (idx(i, m), idx(i + 1, m + 1), idx(i + 1, m))]
+        for m in range(k):
+            tri += [(pa, idx(0, m + 1), idx(0, m)), (pb, idx(n - 1, m), idx(n - 1, m + 1))]
+        faces.append(torch.tensor(tri, dtype=torch.int64))
+        labels.append(torch.full((len(tri),), j, dtype=torch.int64))
+        n_v += n * k + 2
+    V = torch.cat(verts).float()
+    Jf = J.float()
+    d2 = torch.cdist(V, Jf).square()
+    near = torch.topk(d2, 4, dim=1, largest=False)
+    W = torch.zeros(V.shape[0], 24)
+    W.scatter_(1, near.indices, torch.softmax(-near.values / 0.01, dim=1))
+    return Jf, V.contiguous(), W.contiguous(), torch.cat(faces).contiguous(), torch.cat(labels).contiguous()
+
+
+def _random_pose(J, g, pose_scale):
+    aa = (torch.rand(24, 3, generator=g) - 0.5) * 2 * pose_scale
+    aa[0] = 0
+    return forward_kinematics(J, _axis_angle_to_matrix(aa) if pose_scale > 0 else torch.eye(3).repeat(24, 1, 1))
+
+
+def make_mesh_conditions(batch, seed=0, pose_scale=0.5, scale=0.8):
+    """`conditions` of make_conditions' schema on the tube_body mesh (random pose per item, drawn as make_conditions draws
+    them), and the mesh topology: -> (cond, faces [F,3] int64, faces_to_labels [F] int64).  The cameras are those of the
+    canonical view; CameraPreprocessor.forward_with_rotation sets per-item views."""
+    J, V, W, faces, labels = tube_body()
+    n = V.shape[0]
+    flip = torch.eye(4)
+    flip[:3, :3] = _rot_x(math.pi)
+    g = torch.Generator().manual_seed(2000 + seed)
+    verts, fks, joints = [], [], []
+    for _ in range(batch):
+        A, posed = _random_pose(J, g, pose_scale)
+        A = flip[None] @ A
+        VA = torch.einsum("vj,jab->vab", W, A)
+        verts.append(torch.einsum("vab,vb->va", VA, torch.cat([V, torch.ones(n, 1)], 1))[:, :3])
+        fks.append(A)
+        joints.append(posed @ flip[:3, :3].T)
+    T = torch.eye(4)
+    T[2, 3] = FOCAL / scale
+    body_rot = torch.eye(4)
+    body_rot[:3, :3] = _rot_x(math.pi)
+    tp = V.clone()
+    tp[:, 1] += 0.35
+    K = torch.eye(4)
+    K[0, 0] = K[1, 1] = FOCAL
+    rep = lambda t: t[None].repeat(batch, *([1] * t.dim())).contiguous()                  # noqa: E731
+    cond = {"skeletons_xyz": torch.stack(joints).contiguous(), "vertices": torch.stack(verts).contiguous(),
+            "fk_matrices": torch.stack(fks).contiguous(), "cam2world_matrices": rep(torch.inverse(T @ body_rot)),
+            "tpose_vertices": rep(tp), "lbs_weights": rep(W), "intrinsics": rep(K), "scales": torch.full((batch,), float(scale)),
+            "R": rep(torch.eye(4)), "T": rep(T), "full_pose": torch.eye(3)[None, None].repeat(batch, 24, 1, 1)}
+    return cond, faces, labels
+
+
+def make_smpl_record(seed=0, pose_scale=0.5, scale=0.8):
+    """One SMPL regression record of the shape lib/data/conditions.preprocess_smpl_fix_body reads, on the tube_body mesh, plus
+    the assets the front-end needs beside it (joints_index, smpl_tpose_vertices, faces, faces_to_labels): a dict of numpy
+    arrays, what `--smpl-record` of the sample app loads from an .npz."""
+    J, V, W, faces, labels = tube_body()
+    g = torch.Generator().manual_seed(2000 + seed)
+    A, posed = _random_pose(J, g, pose_scale)
+    return {"orig_cam": torch.tensor([[2 * scale, 2 * scale, 0.0, 0.0]]).numpy(), "joints": posed[None].numpy(),
+            "full_pose": torch.eye(3)[None, None].repeat(1, 24, 1, 1).numpy(), "tpose_vertices": V[None].numpy(),
+            "fk_matrices": A[None].numpy(), "lbs_weights": W.numpy(), "betas": torch.zeros(1, 10).numpy(),
+            "joints_index": torch.arange(24).numpy(), "smpl_tpose_vertices": V.numpy(), "faces": faces.numpy(),
+            "faces_to_labels": labels.numpy()}

@@ -803,6 +803,26 @@ int h3d_spectral_norm(const float* W, const float* u, float* u_out, float* u_buf
 int h3d_spectral_norm_bwd(const float* G, const float* W_sn, const float* u, const float* v, const float* sigma, float* dW,
                           float* scratch, int R, int K, h3d_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Mesh rasteriser == SHHQPreprocessor._forward_rasterize (lib/data/preprocessor.py:138-176): pytorch3d 0.6.2 MeshRasterizer with
+ * faces_per_pixel=1, blur_radius=0, PerspectiveCameras(focal_length=focal, R, T, in_ndc=True), plus the reference's post-processing
+ * (:156-174) in the epilogue.  One topology for the batch, per-item vertices and cameras:
+ *   vertices [B,V,3] fp32, faces [F,3] int32, R [B,3,3] row-major, T [B,3]: view X = v @ R + T (row vectors);
+ *   NDC x = focal * X / Z, y = focal * Y / Z; pixel (r, c) sits at (W/s - (2c+1)/s, H/s - (2r+1)/s), s = min(H, W).
+ * A face is skipped when |area| <= 1e-8 in NDC, a vertex has Z <= 0, or an index lies outside [0, V).  A pixel is covered when all
+ * three perspective-corrected barycentrics are > 0 (no culling of either winding); depth pz = sum w'_i Z_i; the smallest pz wins,
+ * exact ties go to the lower face index (deterministic).
+ * Outputs (all but pix_to_face may be NULL):
+ *   pix_to_face [B,H,W] int32 per-image face index or -1;  zbuf [B,H,W] pz or -1;  bary [B,H,W,3] w' or -1;
+ *   segments [B,H,W] int64 = face_labels[f] + 2, 1 for background (needs face_labels [F] int32);
+ *   semantics [B,3,H,W] fp32 = sem_table[faces[f][argmax w']] (first maximum), 0 for background (needs sem_table [V,3]).
+ * workspace: h3d_mesh_raster_bytes(B, F) bytes, 16-byte aligned.  Two launches (per-face setup, 16 x 16 pixel tiles). */
+int64_t h3d_mesh_raster_bytes(int B, int F);
+int h3d_mesh_rasterize(const float* vertices, const int32_t* faces, const float* R, const float* T, float focal,
+                       const int32_t* face_labels, const float* sem_table, int32_t* pix_to_face, float* zbuf, float* bary,
+                       int64_t* segments, float* semantics, void* workspace, int B, int V, int F, int H, int W,
+                       h3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
