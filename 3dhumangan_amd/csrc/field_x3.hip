@@ -51,15 +51,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr float kSA = 1.f;         // activation scale: none -- the matrix cores honour f16 subnormals (tools/probes/denorm_probe.hip),
                                    // so hi = f16(y), lo = f16(y - hi) keeps |error| <= 2^-25 for |y| <= 1 without pre-scaling
 constexpr float kSIn = 64.f;       // input scale (coords / geometry features, |x| < 1000)
-#ifndef H3D_FIELD_LOOK
-#define H3D_FIELD_LOOK 2
-#endif
-#ifndef H3D_FIELD_VALU
-#define H3D_FIELD_VALU 4
-#endif
-constexpr int kLookF = H3D_FIELD_LOOK;          // weight-fragment look-ahead in tile pairs
+constexpr int kLookF = 2;                       // weight-fragment look-ahead in tile pairs
 constexpr int kValuF2 = 0;                      // x2: no forced VALU / MFMA interleave (measured: 17.19 -> 16.86 ms vs 4; 3 and 8 in between)
-constexpr int kValuF = H3D_FIELD_VALU;          // VALU instructions slotted behind each MFMA of a section carrying epilogue work
+constexpr int kValuF = 4;                       // VALU instructions slotted behind each MFMA of a section carrying epilogue work
 
 // per-step activation tables (A1, A0) in LDS
 enum { ST_COORD = 0, ST_GEO, ST_FILM0, ST_FILM1, ST_FILM2, ST_FILM3, ST_COLOR, ST_COUNT };
@@ -303,11 +297,7 @@ __device__ __forceinline__ void layer(f32x16 (&dst)[NT], half8 (&xh)[2 * NT + 1]
     };
     if constexpr (HEAD) load_head(0);
     __builtin_amdgcn_sched_barrier(0);
-#ifdef H3D_FIELD_NO_PREFETCH_PIN
-    constexpr bool kPre = false;
-#else
     constexpr bool kPre = X2 && PER == 1 && !std::is_same<PROD, NoProducer>::value;       // one chunk per section: one prefetch per section
-#endif
     auto pre = [&](auto gc) __attribute__((always_inline)) {
         constexpr int g = decltype(gc)::value;
         constexpr int t = g / W + 1, j = g % W;
@@ -358,10 +348,7 @@ __device__ __forceinline__ void input_layer(f32x16 (&dst)[NT], const half8 (&ih)
 }
 
 
-#ifndef H3D_FIELD_RINGX2
-#define H3D_FIELD_RINGX2 8
-#endif
-constexpr int kRingX2 = H3D_FIELD_RINGX2;       // x2: one more buffer, the refill lags one stage (WeightRing LAG = 1)
+constexpr int kRingX2 = 8;                      // x2: one more buffer, the refill lags one stage (WeightRing LAG = 1)
 
 template <int NT, bool FUSED, bool X2, bool GEOIN = false>
 __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
@@ -448,8 +435,6 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
     const int unit = FUSED ? (S > 32 ? S : 32) : 32;          // samples a wave walks per unit (whole rays when fused)
     const int steps = unit / 32;
     const int seglen = FUSED ? (S < 32 ? S : 32) : 32;
-    H3D_TRACE_INIT();
-    H3D_TRACE(0);
     typedef typename std::conditional<X2, WeightRing<NT, kRingX2, 1>, WeightRing<NT>>::type Ring;
     Ring ring;
     ring.init(A.blob + L.w[0], ring_lds, L.stages, wave, lane);
@@ -518,7 +503,6 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
         const float* tfeat = tfeat0 + opaque;
         const unsigned char* head_lds = head0 + opaque;
 
-        H3D_TRACE(6);
         half8 xh[KS + 1], xl[KS + 1];
         i32x8 b6[NT];
         f32x16 hacc;
@@ -631,7 +615,6 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
         }
         layer<NT, KS + 1, true, false, true, X2>(X, xh, xl, b6, ring, p_f3, p_col, hacc, head_lds, lane);
         pin_agpr<NT>(X);
-        H3D_TRACE(7);
         // density of this lane's sample: head row 0 = accumulator register 0 of the lower lane half
         const float sigma = __shfl(hacc[0], m, 64) * hi0 + hb0;
         float w = 0.f, bg = 0.f;
@@ -708,7 +691,6 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
             rgb[2] = 1.f / (1.f + expf(-(c2 * hi3 + hb3)));
         }
         f32x16 (&acc)[NT] = Y;
-        H3D_TRACE(5);
         if (!FUSED) {
             if (ok && h == 0) {
                 a_out[gi * (F + 4) + 0] = rgb[0];
@@ -812,13 +794,11 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
     }
     }   // unit groups
     ring.drain();
-    H3D_TRACE(9);
-    H3D_TRACE_DUMP(A.out);
 }
 
 size_t lds_bytes(const LayoutX3& L, bool geoin = false) {
     return sizeof(float) * ((size_t)ST_COUNT * 2 * L.HdP + L.HdP + 4 * 64 + (geoin ? kJointRows * 4 : 0)) +
-           (size_t)4 * (L.head_planes * L.KS * 32 + kHeadPad) + (L.head_planes == 3 ? kRingX2 : H3D_RING_DEPTH) * (size_t)L.NT * 2048;
+           (size_t)4 * (L.head_planes * L.KS * 32 + kHeadPad) + (L.head_planes == 3 ? kRingX2 : kWeightRingDepth) * (size_t)L.NT * 2048;
 }
 
 template <int NT, bool FUSED, bool X2, bool GEOIN = false>
@@ -1392,30 +1372,6 @@ static int render_fused_x(bool x2, const void* packed, const float* points, cons
             return H3D_ELAUNCH;
         }
     }
-#ifdef H3D_EXPERIMENT_TRACE
-    {   // development build: dump the cycle trace of workgroup (1000, 3) to $H3D_TRACE_FILE after every launch
-        static unsigned long long* tb = nullptr;
-        if (!tb) (void)hipMalloc(&tb, 4096 * 8);
-        (void)hipMemset(tb, 0, 4096 * 8);
-        A.out = reinterpret_cast<float*>(tb);
-        const int rc2 = launch<true>(A, B, groups, static_cast<hipStream_t>(stream));
-        (void)hipDeviceSynchronize();
-        static unsigned long long host[4096];
-        (void)hipMemcpy(host, tb, sizeof(host), hipMemcpyDeviceToHost);
-        if (const char* f = getenv("H3D_TRACE_FILE")) {
-            if (FILE* fp = fopen(f, "w")) {
-                unsigned long long t0 = host[0] >> 8, prev = t0;
-                for (int i = 0; i < 4096 && host[i]; ++i) {
-                    const unsigned long long tt = host[i] >> 8;
-                    fprintf(fp, "%llu %llu +%llu\n", host[i] & 255ull, tt - t0, tt - prev);
-                    prev = tt;
-                }
-                fclose(fp);
-            }
-        }
-        return rc2;
-    }
-#endif
     return launch<true>(A, B, groups, static_cast<hipStream_t>(stream));
 }
 

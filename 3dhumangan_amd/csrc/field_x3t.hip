@@ -164,8 +164,6 @@ __global__ __launch_bounds__(256, 1) void field_x3t_kernel(Args A) {
         }
     }
 
-    H3D_TRACE_INIT();
-    H3D_TRACE(0);
     const int group_pts = FUSED ? (S > 64 ? S : 64) : 64;
     const int tiles = group_pts / 64;
     const int seglen = FUSED ? (S < 64 ? S : 64) : 64;
@@ -194,11 +192,7 @@ __global__ __launch_bounds__(256, 1) void field_x3t_kernel(Args A) {
         int opaque = 0;
         asm volatile("" : "+s"(opaque));
         const unsigned char* wblob = blob + opaque;
-#ifdef H3D_EXPERIMENT_ALIAS_W        // timing experiment (wrong results): every hidden matrix reads FiLM 1's bytes (0.8 MB: L2-resident)
-        auto wmat = [&](int wi) { return wblob + L.w[wi >= W_F0 ? W_F1 : wi]; };
-#else
         auto wmat = [&](int wi) { return wblob + L.w[wi]; };
-#endif
         // tile stride of matrix wi and byte offset of its k-step ks0 (a K-tile boundary, or the colour layer's trailing k-step)
         auto wstride = [&](int wi) { return tile_bytes_of(wi, KS, X2); };
         auto woff = [&](int wi, int ks0) { return (X2 && wi >= W_F0) ? x3t_kstep_off<true>(ks0) : x3t_kstep_off<false>(ks0); };
@@ -414,7 +408,6 @@ __global__ __launch_bounds__(256, 1) void field_x3t_kernel(Args A) {
             }
         }
         __syncthreads();          // inputs (and, first tile, the tables) visible; previous tile's readers are done
-        H3D_TRACE(1);
 
         f32x16 acc[NU], acc2[NU];
         X3tRing<NTF + NX> ring;     // weight fragments in flight; the next GEMM's first k-steps are requested before the
@@ -423,54 +416,36 @@ __global__ __launch_bounds__(256, 1) void field_x3t_kernel(Args A) {
         zero(acc);
         gemm_x3t<F16, NTF, NX, false, true>(acc, inT + IN_COORD * 2048, in_stride, wmat(W_COORD), wstride(W_COORD), 0, 1, U, lane, ring);
         x3t_prefetch<NTF, NX, P>(ring, wmat(W_F0), wstride(W_F0), 0, U, lane);
-        H3D_TRACE(2);
         store_film(acc, ST_COORD);
-        H3D_TRACE(3);
         __syncthreads();
-        H3D_TRACE(4);
         zero(acc2);
         gemm_x3t<F16, NTF, NX, false, false, true, P>(acc2, actT, act_stride, wmat(W_F0), wstride(W_F0), 0, KS, U, lane, ring);
-        H3D_TRACE(5);
         // ---- geometry layer (K = 31) -> sine -> FiLM 0, geometry half (same accumulators)
         zero(acc);
         gemm_x3t<F16, NTF, NX, false, true>(acc, inT + IN_GEO * 2048, in_stride, wmat(W_GEO), wstride(W_GEO), 0, 2, U, lane, ring);
         x3t_prefetch<NTF, NX, P>(ring, wmat(W_F0), wstride(W_F0), woff(W_F0, KS), U, lane);
-        H3D_TRACE(6);
         __syncthreads();          // every wave has finished reading the coordinate activations
-        H3D_TRACE(7);
         store_film(acc, ST_GEO);
-        H3D_TRACE(8);
         __syncthreads();
-        H3D_TRACE(9);
         gemm_x3t<F16, NTF, NX, false, false, true, P>(acc2, actT, act_stride, wmat(W_F0), wstride(W_F0), woff(W_F0, KS), KS, U, lane, ring);
         x3t_prefetch<NTF, NX, P>(ring, wmat(W_F1), wstride(W_F1), 0, U, lane);
-        H3D_TRACE(10);
         __syncthreads();
-        H3D_TRACE(11);
         store_film(acc2, ST_FILM0);
-        H3D_TRACE(12);
         __syncthreads();
-        H3D_TRACE(13);
         // ---- FiLM 1..3
 #pragma unroll 1
         for (int l = 1; l < 4; ++l) {
             zero(acc);
             gemm_x3t<F16, NTF, NX, false, false, true, P>(acc, actT, act_stride, wmat(W_F0 + l), wstride(W_F0 + l), 0, KS, U, lane, ring);
             x3t_prefetch<NTF, NX, P>(ring, wmat(W_F0 + l + 1), wstride(W_F0 + l + 1), 0, U, lane);      // FiLM l+1, or the colour layer
-            H3D_TRACE(14);
             __syncthreads();
-            H3D_TRACE(15);
             store_film(acc, ST_FILM0 + l);
-            H3D_TRACE(16);
             __syncthreads();
-            H3D_TRACE(17);
         }
 
         // ---- density head (and, unused here, the colour heads of the same tile) on the matrix cores
         heads();
-        H3D_TRACE(18);
         __syncthreads();
-        H3D_TRACE(19);
         if (t < 64) {
             const float sigma = head_value(0, t);
             const int64_t n = n0 + t;
@@ -521,29 +496,21 @@ __global__ __launch_bounds__(256, 1) void field_x3t_kernel(Args A) {
             }
         }
 
-        H3D_TRACE(20);
         // ---- colour FiLM on [x, dir]: KS k-steps over the hidden features + one k-step carrying the view direction
         zero(acc);
         gemm_x3t<F16, NTF, NX, false, false, true, P>(acc, actT, act_stride, wmat(W_COLOR), wstride(W_COLOR), 0, KS, U, lane, ring);
         gemm_x3t<F16, NTF, NX, false, true>(acc, inT + IN_DIR * 2048, in_stride, wmat(W_COLOR), wstride(W_COLOR), woff(W_COLOR, KS), 1, U, lane, ring);
         x3t_prefetch<NTF, NX, P>(ring, wmat(W_FEAT), wstride(W_FEAT), 0, U, lane);
-        H3D_TRACE(21);
         __syncthreads();
-        H3D_TRACE(22);
         store_film(acc, ST_COLOR);
-        H3D_TRACE(23);
         __syncthreads();
-        H3D_TRACE(24);
 
         // ---- colour heads (rows 1..3 of the head tile) and feature head (operands swapped: rows = samples)
         heads();
-        H3D_TRACE(25);
         f32x16 (&accF)[NU] = acc2;
         zero(accF);
         gemm_x3t<F16, NTF, NX, true, false, true, P>(accF, actT, act_stride, wmat(W_FEAT), wstride(W_FEAT), 0, KS, U, lane, ring);
-        H3D_TRACE(26);
         __syncthreads();
-        H3D_TRACE(27);
         if (t < 192) {
             const int c = t >> 6, mm_ = t & 63;
             const float v = head_value(1 + c, mm_);
@@ -645,12 +612,9 @@ __global__ __launch_bounds__(256, 1) void field_x3t_kernel(Args A) {
                 }
             }
         }
-        H3D_TRACE(28);
         __syncthreads();     // actT / inT / part / wgt are rewritten by the next tile
-        H3D_TRACE(29);
     }
     }   // sample groups
-    H3D_TRACE_DUMP(A.out);
 }
 
 size_t lds_bytes(const LayoutT& L) {
@@ -908,32 +872,6 @@ extern "C" int h3d_render_fused_x3t_tier(const void* packed, const float* points
     const int group = S > 64 ? S : 64;
     const int64_t groups = (N + group - 1) / group;
     H3D_REQUIRE(groups < (int64_t(1) << 31), "h3d_render_fused_x3t: too many rays");
-#ifdef H3D_EXPERIMENT_TRACE
-    {   // development build: dump the cycle trace of workgroup (1000, 3) to $H3D_TRACE_FILE after every launch
-        static unsigned long long* tb = nullptr;
-        if (!tb) (void)hipMalloc(&tb, 4096 * 8);
-        (void)hipMemset(tb, 0, 4096 * 8);
-        A.out = reinterpret_cast<float*>(tb);
-        const int rc2 = products == 3 ? launch<true, 3>(A, B, groups, static_cast<hipStream_t>(stream))
-                      : products == 4 ? launch<true, 4>(A, B, groups, static_cast<hipStream_t>(stream))
-                                      : launch<true, 1>(A, B, groups, static_cast<hipStream_t>(stream));
-        (void)hipDeviceSynchronize();
-        static unsigned long long host[4096];
-        (void)hipMemcpy(host, tb, sizeof(host), hipMemcpyDeviceToHost);
-        if (const char* f = getenv("H3D_TRACE_FILE")) {
-            if (FILE* fp = fopen(f, "w")) {
-                unsigned long long t0 = host[0] >> 8, prev = t0;
-                for (int i = 0; i < 4096 && host[i]; ++i) {
-                    const unsigned long long tt = host[i] >> 8;
-                    fprintf(fp, "%llu %llu +%llu\n", host[i] & 255ull, tt - t0, tt - prev);
-                    prev = tt;
-                }
-                fclose(fp);
-            }
-        }
-        return rc2;
-    }
-#endif
     return products == 3 ? launch<true, 3>(A, B, groups, static_cast<hipStream_t>(stream))
          : products == 4 ? launch<true, 4>(A, B, groups, static_cast<hipStream_t>(stream))
                          : launch<true, 1>(A, B, groups, static_cast<hipStream_t>(stream));

@@ -30,21 +30,12 @@ namespace {
 
 typedef BF16::vec8 bf8;
 constexpr int kShared = 128;
-#ifndef H3D_SYNTH_RING
-#define H3D_SYNTH_RING 4
-#endif
-constexpr int kRingDepth = H3D_SYNTH_RING;
+constexpr int kRingDepth = 4;      // 4 x 16 KB: leaves ~96 KB of LDS for the per-layer tables
 constexpr int kDescInts = 12;       // descriptor fields per block kept in LDS (multiple of 4: the ring behind them stays 16-byte aligned)
-#ifndef H3D_SYNTH_VALU
-#define H3D_SYNTH_VALU 5
-#endif
-constexpr int kValuPerMfma = H3D_SYNTH_VALU;
-constexpr int kValuPerMfmaX2 = 0;  // x2: the scheduler places the producers' VALU work itself (24.27 -> 24.11 ms vs 5)    // VALU instructions slotted behind each MFMA of a section that carries epilogue work
-#ifndef H3D_SYNTH_LOOK_X2
-#define H3D_SYNTH_LOOK_X2 2
-#endif
+constexpr int kValuPerMfma = 5;    // VALU instructions slotted behind each MFMA of a section that carries epilogue work
+constexpr int kValuPerMfmaX2 = 0;  // x2: the scheduler places the producers' VALU work itself (24.27 -> 24.11 ms vs 5)
 constexpr int kLook = 2;           // weight-fragment look-ahead in tile pairs (gemm_x3_roll)
-template <int NT> constexpr int look_x2() { return H3D_SYNTH_LOOK_X2 < NT / 2 ? H3D_SYNTH_LOOK_X2 : NT / 2; }   // x2: sections are shorter      // 4 x 16 KB: leaves ~96 KB of LDS for the per-layer tables
+template <int NT> constexpr int look_x2() { return 2 < NT / 2 ? 2 : NT / 2; }   // x2: sections are shorter
 
 struct Args {
     const unsigned char* stream;
@@ -251,7 +242,6 @@ __device__ __forceinline__ void conv_progressive(f32x16 (&dst)[NT], V8 (&xh)[2 *
     prod.prime();
     static_for<0, 8>([&](auto c) __attribute__((always_inline)) { prod.template chunk<0, decltype(c)::value>(); });
     __builtin_amdgcn_sched_barrier(0);
-    H3D_TRACE(30);
     constexpr int W = NT, PER = 8 / W;          // sections per 2-k-step window, chunks per section
     auto hook = [&](auto gc) __attribute__((always_inline)) {
         constexpr int g = decltype(gc)::value;
@@ -345,8 +335,6 @@ __global__ __launch_bounds__(256, 1) void synthesis_x3_kernel(Args A) {
     }
     __syncthreads();
 
-    H3D_TRACE_INIT();
-    H3D_TRACE(0);
     WeightRing<NT, DEPTH + (X2 ? 1 : 0), X2 ? 1 : 0> ring;        // x2: the fp6 records span two stages (LAG = 1)
     ring.init(A.stream, ring_lds, A.total_stages, wave, lane);
 
@@ -637,7 +625,6 @@ __global__ __launch_bounds__(256, 1) void synthesis_x3_kernel(Args A) {
     // ================= blocks from the first skip connection on (constant style only) ============================
     // conv 0 goes x -> acc (x stays live as the residual), conv 1 goes acc -> x accumulating onto the residual
     // (conv biases are folded into the consumers' tables by the host: build_x3 in synthesis_pack.py).
-    H3D_TRACE_RESET();
 #pragma unroll 1
     for (int blk = first_skip; blk < n_blocks; ++blk) {
         int opaque = 0;
@@ -646,18 +633,12 @@ __global__ __launch_bounds__(256, 1) void synthesis_x3_kernel(Args A) {
         const float* abt = ab0 + opaque;
         f32x16 acc[NT];
         pin_agpr<NT>(x);
-        H3D_TRACE(20);
         {   // conv 0, with the ToRGB of the previous skip block's output (this block's input x) riding along
             const float* wr_prev = (blk > first_skip && dget(blk - 1, 0)) ? tab + dget(blk - 1, 1) : zero0 + opaque;
-#ifdef H3D_EXPERIMENT_NO_RGB
-            SpadeProducer<NT, true, false, X2, frag8> prod{x, xh, xl, b6, lane_base(abt + dget(blk, 3) * 2 * HdP, 32 * h), lane_base(wr_prev, 16 * h), rgb_acc, gmax};
-#else
             SpadeProducer<NT, true, !kHeads, X2, frag8> prod{x, xh, xl, b6, lane_base(abt + dget(blk, 3) * 2 * HdP, 32 * h), lane_base(wr_prev, 16 * h), rgb_acc, gmax};
-#endif
             conv_progressive<NT, true, X2>(acc, xh, xl, b6, ring, prod);
         }
         pin_agpr<NT>(x); pin_agpr<NT>(acc);
-        H3D_TRACE(21);
         {
             SpadeProducer<NT, true, false, X2, frag8> prod{acc, xh, xl, b6, lane_base(abt + dget(blk, 7) * 2 * HdP, 32 * h), nullptr, rgb_acc, gmax};
             if constexpr (kHeads) {
@@ -672,14 +653,12 @@ __global__ __launch_bounds__(256, 1) void synthesis_x3_kernel(Args A) {
             rgb_acc[0] += wb[0]; rgb_acc[1] += wb[1]; rgb_acc[2] += wb[2];
         }
     }
-    H3D_TRACE(5);
     if (n_blocks > first_skip && dget(n_blocks - 1, 0)) to_rgb(tab0 + dget(n_blocks - 1, 1), false);
     if constexpr (kHeads) {
         // the head tile: every lane holds the complete sums of its pixel (rows = heads, replicated); the store below adds the two
         // lane halves, so only one of them contributes
         if (h == 0) { rgb_acc[0] += hacc[0]; rgb_acc[1] += hacc[1]; rgb_acc[2] += hacc[2]; }
     }
-    H3D_TRACE(6);
     if (SEG && A.store_state) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
@@ -703,8 +682,6 @@ __global__ __launch_bounds__(256, 1) void synthesis_x3_kernel(Args A) {
         if (A.ovf && !(gmax < kX2ActLimit)) atomicOr(A.ovf + b, 1);
     }
     ring.drain();
-    H3D_TRACE(9);
-    H3D_TRACE_DUMP(A.state);
 }
 
 size_t lds_bytes(const Args& A, int NT, int depth) {
@@ -864,18 +841,12 @@ static int synthesis_x(bool x2, const void* stream, int64_t total_stages, const 
     H3D_REQUIRE(groups < (int64_t(1) << 31), "h3d_synthesis_x3: image too large");
     hipStream_t st = static_cast<hipStream_t>(stream_);
     const bool heads = A.heads != 0;                                 // x2 plans: ToRGB head tables present
-#ifdef H3D_DEV_ONLY_HOT       // development: compile only the instantiation the BASELINE cfg-3 bench runs (fast ISA / resource turnaround)
-    (void)deep;
-    return A.mid_x3 ? launch_seg<8, kRingDepth, false, true, true, true>(A, B, groups, st)
-         : heads ? launch_seg<8, kRingDepth, false, true, true>(A, B, groups, st) : launch_seg<8, kRingDepth, false, true>(A, B, groups, st);
-#else
     if (x2) {
         if (NT == 8) return deep ? launch_one<8, 6, true>(A, B, groups, st, heads) : launch_one<8, kRingDepth, true>(A, B, groups, st, heads);
         return deep ? launch_one<4, 6, true>(A, B, groups, st, heads) : launch_one<4, kRingDepth, true>(A, B, groups, st, heads);
     }
     if (NT == 8) return deep ? launch_one<8, 6, false>(A, B, groups, st) : launch_one<8, kRingDepth, false>(A, B, groups, st);
     return deep ? launch_one<4, 6, false>(A, B, groups, st) : launch_one<4, kRingDepth, false>(A, B, groups, st);
-#endif
 }
 
 extern "C" int h3d_synthesis_x3(const void* stream, int64_t total_stages, const float* tables, int table_floats,

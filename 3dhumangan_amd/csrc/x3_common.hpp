@@ -29,9 +29,7 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
-#ifndef H3D_RING_DEPTH
-#define H3D_RING_DEPTH 7
-#endif
+constexpr int kWeightRingDepth = 7;      // stages of the shared weight ring (WeightRing's default DEPTH)
 
 struct F16 {          // scaled f16 halves
     typedef _Float16 elem;
@@ -126,10 +124,7 @@ __device__ __forceinline__ f32x4 ldt4_pinned(lds_ptr base, int float_index) {
 // which is ordered against the (asm volatile) DMA issues: round 3's index arithmetic (stage index * 16 KiB as a 64-bit shift,
 // buffer index * 16 KiB, 64-bit vector adds per stage) was hoisted by the compiler to the head of each GEMM, sixteen stages
 // at a time, and spilled from there (v_writelane: 129 spilled SGPRs in synthesis_x3_kernel<8, 4, false, true>).
-#ifndef H3D_DMA_SLOT
-#define H3D_DMA_SLOT 0
-#endif
-template <int NT, int DEPTH = H3D_RING_DEPTH, int LAG = 0>
+template <int NT, int DEPTH = kWeightRingDepth, int LAG = 0>
 struct WeightRing {
     static constexpr int kBuf = DEPTH;
     static_assert(DEPTH - LAG >= 3 && (DEPTH - 2 - LAG) * (NT * 2 / 4) < 64, "ring depth out of range for the 6-bit vmcnt field");
@@ -144,13 +139,8 @@ struct WeightRing {
     unsigned read_at, rd_begin, rd_end;     // LDS address of the buffer acquired next / of the ring / past it
     int vslot;                              // vector: this lane's 16 bytes inside a stage = (wave * kChunks) KiB + lane * 16
     int lane;
-    int wave;                               // scalar: this wave's index in the workgroup (staggered refills)
-    bool primed = false;                    // experiments only
 
     __device__ __forceinline__ void init(const unsigned char* stream, unsigned char* lds, int total_stages, int w, int l) {
-#ifdef H3D_EXPERIMENT_SMALL_STREAM
-        total_stages = total_stages < 8 ? total_stages : 8;        // timing experiment: the stream wraps inside 128 KB (always L2 hits; wrong results)
-#endif
         g_begin = fill_g = stream;
         g_end_lo = (unsigned)(size_t)stream + (unsigned)total_stages * kStage;
         rd_begin = read_at = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
@@ -159,23 +149,9 @@ struct WeightRing {
         m0_end = m0_begin + kRingBytes;
         vslot = w * kChunks * 1024 + l * 16;
         lane = l;
-        wave = w;
         asm volatile("" : "+s"(fill_g), "+s"(fill_m0), "+s"(read_at));
 #pragma unroll
         for (int i = 0; i < kBuf - 1 - LAG; ++i) issue();
-        primed = true;
-    }
-    // Staggered refill (H3D_RING_STAGGER): the kChunks pieces a wave owes per stage are issued in ONE section of the k-step,
-    // a different one for each wave (section c <-> wave c), instead of one piece per section by all four waves at once: the
-    // waves of a workgroup run in lockstep between barriers, so their pieces otherwise arrive at the CU's vector-memory path
-    // together and queue behind each other (issue cost of a piece: ~60 cycles alone, 100-185 in a crowd, MI355X_MICROARCH.md).
-    template <int C>
-    __device__ __forceinline__ void issue_slot() {
-#ifdef H3D_RING_STAGGER
-        if ((wave % kChunks) == C) issue();
-#else
-        issue_chunk<C>();
-#endif
     }
     // One 1 KB piece of the stage being filled.  Issued through inline asm on purpose: hipcc models
     // global_load_lds as a FLAT access that touches both LDS and memory and, while one is pending, degrades EVERY
@@ -188,24 +164,8 @@ struct WeightRing {
     // every write of M0 in it is one of these).
     template <int C>
     __device__ __forceinline__ void issue_chunk() {           // C = 0 .. kChunks-1, in order
-#ifdef H3D_EXPERIMENT_NO_DMA                                  // timing experiment (wrong results): the refills are never issued
-        if (primed) return;
-#endif
-#ifndef H3D_RING_M0_PER_PIECE
-#if !defined(H3D_RING_POLICY_ID) || H3D_RING_POLICY_ID == 0      // cache-policy bits of the refill (experiments: 1 nt, 2 sc0, 3 sc1)
-#define H3D_RING_POLICY ""
-#elif H3D_RING_POLICY_ID == 1
-#define H3D_RING_POLICY " nt"
-#elif H3D_RING_POLICY_ID == 2
-#define H3D_RING_POLICY " sc0"
-#else
-#define H3D_RING_POLICY " sc1"
-#endif
-        if (C == 0) asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2 offset:0" H3D_RING_POLICY : : "s"(fill_m0), "v"(vslot), "s"(fill_g) : "m0");
-        else asm volatile("global_load_lds_dwordx4 %0, %1 offset:%2" H3D_RING_POLICY : : "v"(vslot), "s"(fill_g), "n"(C * 1024));
-#else
-        asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%3" : : "s"(fill_m0), "v"(vslot), "s"(fill_g), "n"(C * 1024) : "m0");
-#endif
+        if (C == 0) asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2 offset:0" : : "s"(fill_m0), "v"(vslot), "s"(fill_g) : "m0");
+        else asm volatile("global_load_lds_dwordx4 %0, %1 offset:%2" : : "v"(vslot), "s"(fill_g), "n"(C * 1024));
         if (C == kChunks - 1) {
             fill_g += kStage;
             fill_g = (unsigned)(size_t)fill_g == g_end_lo ? g_begin : fill_g;
@@ -243,18 +203,12 @@ struct WeightRing {
     // 360.5 / 359.7 images/s; every convolution shape within 1 %) -- and the distance argument FAILED where several workgroups
     // share a CU: conv_x3.hip at two to four workgroups per CU with another workgroup's moments epilogue loading the LDS pipe
     // returned a tile computed from a half-refilled stage in 1-4 % of launches (profiles/r6_conv_ring_war_race.txt).
-    // H3D_RING_DISTANCE restores the old wait (development only).
     __device__ __forceinline__ lds_ptr acquire() {
         // vmcnt only (expcnt / lgkmcnt fields left at "no wait"): stages t+1 .. t+kBuf-2 may stay in flight
         constexpr int kKeep = (kBuf - 2 - LAG) * kChunks;
-#ifndef H3D_EXPERIMENT_NO_BARRIER
-#ifndef H3D_RING_DISTANCE           // every LDS read of this wave returned before the barrier
+        // lgkmcnt(0): every LDS read of this wave returned before the barrier
         __builtin_amdgcn_s_waitcnt((kKeep & 0xF) | ((kKeep >> 4) << 14) | 0x0070 | 0x0000);
-#else
-        __builtin_amdgcn_s_waitcnt((kKeep & 0xF) | ((kKeep >> 4) << 14) | 0x0070 | 0x0F00);
-#endif
         __builtin_amdgcn_s_barrier();
-#endif
         return slot<4>(next_read());
     }
     // Two consecutive stages (t, t + 1) behind ONE wait + barrier (the x2 GEMM consumes stages in pairs: an fp6 record spans an
@@ -269,14 +223,8 @@ struct WeightRing {
     __device__ __forceinline__ void acquire2(lds_ptr& r0, lds_ptr& r1, lds_ptr& r1c, lds_ptr& r1d, lds_ptr& r1s) {
         static_assert(kBuf - 3 - LAG >= 0, "ring too shallow for paired acquires");
         constexpr int kKeep = (kBuf - 3 - LAG) * kChunks;
-#ifndef H3D_EXPERIMENT_NO_BARRIER
-#ifndef H3D_RING_DISTANCE
         __builtin_amdgcn_s_waitcnt((kKeep & 0xF) | ((kKeep >> 4) << 14) | 0x0070 | 0x0000);
-#else
-        __builtin_amdgcn_s_waitcnt((kKeep & 0xF) | ((kKeep >> 4) << 14) | 0x0070 | 0x0F00);
-#endif
         __builtin_amdgcn_s_barrier();
-#endif
         r0 = slot<4>(next_read());
         const unsigned odd = next_read();
         r1 = slot<4>(odd);
@@ -289,9 +237,6 @@ struct WeightRing {
 
 template <typename T, bool SWAP>
 __device__ __forceinline__ f32x16 mm(const typename T::vec8& w, const typename T::vec8& x, const f32x16& c) {
-#ifdef H3D_EXPERIMENT_NO_MFMA
-    f32x16 r = c; r[0] += (float)w[0] * (float)x[0]; return r;
-#endif
     return SWAP ? T::mfma(x, w, c) : T::mfma(w, x, c);
 }
 
@@ -301,37 +246,6 @@ __device__ __forceinline__ f32x16 mm(const typename T::vec8& w, const typename T
 // the matrix pipe.  Same ring protocol: acquire(s+1) happens inside k-step s, just before the first read of stage
 // s+1 and after the last read of stage s was issued; each acquire is followed by exactly one refill, one DMA chunk
 // after each of the next NT/2 tile pairs.  acc is accumulated into (initialise it with the bias / residual).
-#ifdef H3D_EXPERIMENT_TRACE
-// Development: cycle trace of workgroup (1000, 3), kept in LDS while the kernel runs (a global store per event would wait on
-// vmcnt and drain the weight ring's DMA queue) and copied out at the end (H3D_TRACE_DUMP).
-constexpr int kTraceMax = 500;
-__shared__ unsigned long long h3d_tr_buf[kTraceMax];
-__shared__ int h3d_tr_cnt;
-#define H3D_TRACE(tag)                                                                         \
-    do {                                                                                       \
-        if (blockIdx.x == 1000 && blockIdx.y == 3 && threadIdx.x == 0) {                       \
-            const int n_ = h3d_tr_cnt;                                                         \
-            if (n_ < kTraceMax) {                                                              \
-                h3d_tr_buf[n_] = (__builtin_readcyclecounter() << 8) | (unsigned long long)(tag); \
-                h3d_tr_cnt = n_ + 1;                                                           \
-            }                                                                                  \
-        }                                                                                      \
-    } while (0)
-#define H3D_TRACE_INIT() do { if (threadIdx.x == 0) h3d_tr_cnt = 0; __syncthreads(); } while (0)
-#define H3D_TRACE_RESET() do { if (threadIdx.x == 0) h3d_tr_cnt = 0; } while (0)
-#define H3D_TRACE_DUMP(dst)                                                                    \
-    do {                                                                                       \
-        if (blockIdx.x == 1000 && blockIdx.y == 3 && threadIdx.x == 0) {                       \
-            unsigned long long* d_ = reinterpret_cast<unsigned long long*>(dst);               \
-            for (int i_ = 0; i_ < h3d_tr_cnt; ++i_) d_[i_] = h3d_tr_buf[i_];                   \
-        }                                                                                      \
-    } while (0)
-#else
-#define H3D_TRACE(tag) do { } while (0)
-#define H3D_TRACE_INIT() do { } while (0)
-#define H3D_TRACE_RESET() do { } while (0)
-#define H3D_TRACE_DUMP(dst) do { } while (0)
-#endif
 
 struct NoHook {
     template <typename G> __device__ __forceinline__ void operator()(G) const {}
@@ -360,49 +274,24 @@ __device__ __forceinline__ void gemm_x3_roll(f32x16 (&acc)[NT], const typename T
         constexpr int q = decltype(qc)::value;
         const lds_ptr s = st[(q / P) & 1] + (q % P) * 4096;
         Pair& b = buf[q % NB];
-#ifdef H3D_EXPERIMENT_NO_WREAD
-        if (q >= NB) return;
-#endif
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             b.h[i] = __builtin_bit_cast(typename T::vec8, lds_ld<u32x4>(s + (i * 2 + 0) * 1024));
             b.l[i] = __builtin_bit_cast(typename T::vec8, lds_ld<u32x4>(s + (i * 2 + 1) * 1024));
         }
     };
-    H3D_TRACE(1);
     st[0] = ring.acquire();
     ring.issue();
     static_for<0, L>(load_pair);
     static_for<0, G>([&](auto gc) __attribute__((always_inline)) {
         constexpr int g = decltype(gc)::value;
         constexpr int s = g / P, p = g % P;
-#ifdef H3D_EXPERIMENT_TRACE_FINE
-        if constexpr (s >= 4 && s < 7) H3D_TRACE(10 + p);
-#endif
         if constexpr (p == P - L && s + 1 < KS) {
-            if constexpr (s % 4 == 0) H3D_TRACE(2);
             st[(s + 1) & 1] = ring.acquire();
-            if constexpr (s % 4 == 0) H3D_TRACE(3);
             __builtin_amdgcn_sched_barrier(0);
         }
-        // refill chunk owed to the latest acquire (its place in the section: H3D_DMA_SLOT, an experiment knob; 0 = after the MFMAs)
-        auto dma = [&]() __attribute__((always_inline)) {
-            constexpr int since = g - (P - L);                    // sections since the first in-loop acquire position
-            if constexpr (since >= 0 && since / P + 1 < KS) ring.template issue_slot<since % P>();
-        };
-#if H3D_DMA_SLOT == 1
-        dma();
-#endif
         if constexpr (g + L < G) load_pair(IC<g + L>{});
-#if H3D_DMA_SLOT == 2
-        dma();
-#endif
-#ifndef H3D_EXPERIMENT_NO_HOOK
         hook(gc);
-#endif
-#if H3D_DMA_SLOT == 3
-        dma();
-#endif
         const Pair& b = buf[g % NB];
         constexpr int n0 = 2 * p, n1 = 2 * p + 1;
         constexpr int sx = PAIRK ? 2 * s : s;    // activation fragment of plane 0 (plane 1: the same one, or the next k-step's)
@@ -414,21 +303,16 @@ __device__ __forceinline__ void gemm_x3_roll(f32x16 (&acc)[NT], const typename T
             acc[n0] = mm<T, SWAP>(b.h[0], xh[sx], acc[n0]);
             acc[n1] = mm<T, SWAP>(b.h[1], xh[sx], acc[n1]);
         }
-#if !defined(H3D_EXPERIMENT_PRODUCTS) || H3D_EXPERIMENT_PRODUCTS >= 2      // timing experiments only (wrong results)
         if constexpr (XLO) {
             acc[n0] = mm<T, SWAP>(b.h[0], xl[s], acc[n0]);
             acc[n1] = mm<T, SWAP>(b.h[1], xl[s], acc[n1]);
         }
-#endif
-#if !defined(H3D_EXPERIMENT_PRODUCTS) || H3D_EXPERIMENT_PRODUCTS >= 3
         acc[n0] = mm<T, SWAP>(b.l[0], xh[PAIRK ? sx + 1 : sx], acc[n0]);
         acc[n1] = mm<T, SWAP>(b.l[1], xh[PAIRK ? sx + 1 : sx], acc[n1]);
-#endif
-        // refill chunk owed to the latest acquire: acquires sit at section (s*P + P-L) for s+1 < KS, each followed by
-        // P chunks in the next P sections; the prologue acquire was refilled by ring.issue()
-#if H3D_DMA_SLOT == 0
-        dma();
-#endif
+        // refill chunk owed to the latest acquire, after the section's MFMAs: acquires sit at section (s*P + P-L) for s+1 < KS,
+        // each followed by P chunks in the next P sections; the prologue acquire was refilled by ring.issue()
+        constexpr int since = g - (P - L);                        // sections since the first in-loop acquire position
+        if constexpr (since >= 0 && since / P + 1 < KS) ring.template issue_chunk<since % P>();
         if constexpr (VALU_PER_MFMA > 0) {
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
@@ -442,7 +326,6 @@ __device__ __forceinline__ void gemm_x3_roll(f32x16 (&acc)[NT], const typename T
         asm volatile("" : "+a"(acc[n0]), "+a"(acc[n1]));
         __builtin_amdgcn_sched_barrier(0);
     });
-    H3D_TRACE(4);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- x2
@@ -487,9 +370,6 @@ __device__ __forceinline__ i32x8 x2_record(const F16::vec8& l0, const F16::vec8&
 template <bool SWAP>
 __device__ __forceinline__ f32x16 mm6(const i32x8& w, const i32x8& x, const f32x16& c) {
     const int sw = w[6], sx = x[6];          // the lanes' block scales (weights: 1 / alpha; activations: see x2_record)
-#ifdef H3D_EXPERIMENT_NO_MFMA
-    f32x16 r = c; r[0] += (float)(w[0] + x[0] + sw + sx); return r;
-#endif
     return SWAP ? __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(x, w, c, 2, 2, 0, sx, 0, sw)
                 : __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(w, x, c, 2, 2, 0, sw, 0, sx);
 }
@@ -523,7 +403,6 @@ __device__ __forceinline__ unsigned split2_x2(float a, float b, unsigned& lo) {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     typedef float f2 __attribute__((ext_vector_type(2)));
     const h2 hv = __builtin_convertvector(f2{a, b}, h2);
-#ifndef H3D_X2_SPLIT_PLAIN
     // mixed-precision FMAs read the f16 halves directly and write packed f16: residual (exact), then * 2^12 and the conversion --
     // 5 instructions per pair instead of 8, bit-identical results (synthesis engine 25.6 -> 25.1 ms)
     const unsigned hw = __builtin_bit_cast(unsigned, hv);
@@ -535,16 +414,6 @@ __device__ __forceinline__ unsigned split2_x2(float a, float b, unsigned& lo) {
     asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(lw) : "v"(lb), "s"(kX2Rho));
     lo = lw;
     return hw;
-#else
-    const float fa = (float)hv.x, fb = (float)hv.y;
-    float la, lb;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(la) : "v"(a), "v"(fa));
-    asm("v_sub_f32 %0, %1, %2" : "=v"(lb) : "v"(b), "v"(fb));
-    asm("v_mul_f32 %0, %1, %2" : "=v"(la) : "v"(la), "v"(kX2Rho));
-    asm("v_mul_f32 %0, %1, %2" : "=v"(lb) : "v"(lb), "v"(kX2Rho));
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f2{la, lb}, h2));
-    return __builtin_bit_cast(unsigned, hv);
-#endif
 }
 
 // ... for |a|, |b| < 16 (the field: sine outputs), one instruction less per pair: hi * 2^12 is still an f16 (exact), and one
@@ -552,9 +421,6 @@ __device__ __forceinline__ unsigned split2_x2(float a, float b, unsigned& lo) {
 __device__ __forceinline__ unsigned split2_x2_bounded(float a, float b, unsigned& lo) {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     typedef float f2 __attribute__((ext_vector_type(2)));
-#ifdef H3D_X2_SPLIT_GENERAL
-    return split2_x2(a, b, lo);
-#endif
     const unsigned hw = __builtin_bit_cast(unsigned, __builtin_convertvector(f2{a, b}, h2));
     unsigned hs, lw;
     asm("v_pk_mul_f16 %0, %1, %2" : "=v"(hs) : "v"(hw), "s"(0x6C006C00u));                 // (4096, 4096) as f16
@@ -629,23 +495,9 @@ __device__ __forceinline__ void gemm_x2_roll(f32x16 (&acc)[NT], const F16::vec8 
             else if constexpr (s % 2 == 1) ring.acquire2(st[(s + 1) & 1], st[s & 1], stc[0], stc[1], sts);      // x2: the pair (s + 1, s + 2)
             __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (p == 0) H3D_TRACE(100 + s);
-        auto dma = [&]() __attribute__((always_inline)) {
-            constexpr int since = g - (P - L);
-            if constexpr (since >= 0 && since / P + 1 < KS) ring.template issue_slot<since % P>();
-        };
-#if H3D_DMA_SLOT == 1
-        dma();
-#endif
         pre(gc);
         if constexpr (g + L < G) load_pair(IC<g + L>{});
-#if H3D_DMA_SLOT == 2
-        dma();
-#endif
         hook(gc);
-#if H3D_DMA_SLOT == 3
-        dma();
-#endif
         const Pair& b = buf[g % NB];
         constexpr int n0 = 2 * p, n1 = 2 * p + 1;
         if constexpr (ZERO && s == 0) {
@@ -670,9 +522,8 @@ __device__ __forceinline__ void gemm_x2_roll(f32x16 (&acc)[NT], const F16::vec8 
                 acc[n0 + i] = mm6<SWAP>(w6, b6[s / 2], acc[n0 + i]);
             }
         }
-#if H3D_DMA_SLOT == 0
-        dma();
-#endif
+        constexpr int since = g - (P - L);                        // refill chunk owed to the latest acquire (see gemm_x3_roll)
+        if constexpr (since >= 0 && since / P + 1 < KS) ring.template issue_chunk<since % P>();
         if constexpr (VALU_PER_MFMA > 0) {
 #pragma unroll
             for (int i = 0; i < n_mfma; ++i) {

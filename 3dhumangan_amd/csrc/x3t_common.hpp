@@ -31,10 +31,7 @@
 namespace h3d {
 
 constexpr int kX3tMT = 2;            // sample tiles (of 32) per workgroup
-#ifndef H3D_X3T_DEPTH
-#define H3D_X3T_DEPTH 4
-#endif
-constexpr int kX3tDepth = H3D_X3T_DEPTH;        // weight k-steps in flight per wave (register ring)
+constexpr int kX3tDepth = 4;         // weight k-steps in flight per wave (register ring)
 
 // byte offset of fragment plane (mt, ks, plane) inside an activation tile with KS k-steps per sample tile
 __device__ __forceinline__ int x3t_frag(int KS, int mt, int ks, int plane) { return ((mt * KS + ks) * 2 + plane) * 1024; }
@@ -354,13 +351,7 @@ __device__ __forceinline__ void gemm_x3t(f32x16 (&acc)[2 * NTF + NX], const unsi
         for (int ks = 0; ks < KS - D; ks += D) {
             static_for<0, D>([&](auto dc) __attribute__((always_inline)) {
                 constexpr int d = decltype(dc)::value;
-#ifdef H3D_EXPERIMENT_TRACE_FINE
-                H3D_TRACE(50 + d);                    // before the wait for k-step ks + d
-#endif
                 x3t_wait_frags<kInflight, NA, (X2 ? (d & 1) == 0 : WLO)>(a[d].h, a[d].l);      // (x2c: only even k-steps carry a record)
-#ifdef H3D_EXPERIMENT_TRACE_FINE
-                H3D_TRACE(60 + d);                    // after it
-#endif
                 __builtin_amdgcn_sched_barrier(0);
                 kstep(IC<1>{}, IC<1>{}, IC<(d & 1)>{}, a[d], b[d & 1], a[(d + D - 1) % D], ks + d + D - 1, b[(d + 1) & 1], ks + d + 1);
             });

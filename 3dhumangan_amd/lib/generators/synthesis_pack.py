@@ -670,9 +670,6 @@ class SynthesisPlan:
                     if x3["state"] is None or x3["state"].numel() < need:
                         x3["state"] = torch.empty(need, device=fixed_style.device, dtype=torch.float32)
                     state = x3["state"]
-                if os.environ.get("H3D_SYNTH_TRACE"):          # development: cycle trace of one workgroup (tools/)
-                    x3["trace"] = torch.zeros(4096, dtype=torch.int64, device=fixed_style.device)
-                    state = x3["trace"]
                 lib, rc = _lib.load(), 0
                 entry = lib.h3d_synthesis_x2 if x2 else lib.h3d_synthesis_x3
                 if x2 and self.x2_guard and len(segs) == 1 and state is None:

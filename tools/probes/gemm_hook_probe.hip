@@ -67,7 +67,7 @@ int main(int argc, char** argv) {
     const size_t bytes = (size_t)total * NT * 2048;
     unsigned char* d; float* o;
     hipMalloc(&d, bytes); hipMemset(d, 0, bytes); hipMalloc(&o, 4096);
-    const size_t lds = (size_t)H3D_RING_DEPTH * NT * 2048;
+    const size_t lds = (size_t)kWeightRingDepth * NT * 2048;
     hipFuncSetAttribute(reinterpret_cast<const void*>(probe<8, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
     float best = 1e9;

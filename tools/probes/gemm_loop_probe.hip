@@ -1,6 +1,6 @@
 // Stand-alone timing of the x3 GEMM inner loop (weight ring + 3-product MFMA chain) without any epilogue work:
 // what the loop itself sustains with one wave per SIMD.  Build: hipcc -O3 -std=c++17 --offload-arch=gfx950
-//   -I3dhumangan_amd/csrc -Iinclude [-DH3D_EXPERIMENT_...] tools/probes/gemm_loop_probe.hip -o gemm_loop_probe
+//   -I3dhumangan_amd/csrc -Iinclude tools/probes/gemm_loop_probe.hip -o gemm_loop_probe
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -43,7 +43,7 @@ int main(int argc, char** argv) {
     const size_t bytes = (size_t)total * NT * 2048;
     unsigned char* d; float* o;
     hipMalloc(&d, bytes); hipMemset(d, 0, bytes); hipMalloc(&o, 4096);
-    const size_t lds = (size_t)H3D_RING_DEPTH * NT * 2048;
+    const size_t lds = (size_t)kWeightRingDepth * NT * 2048;
     hipFuncSetAttribute(reinterpret_cast<const void*>(probe<8, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
     for (int it = 0; it < 3; ++it) {

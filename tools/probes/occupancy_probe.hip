@@ -53,7 +53,7 @@ int main(int argc, char** argv) {
     unsigned char* d; float* o;
     hipMalloc(&d, bytes); hipMemset(d, 0, bytes); hipMalloc(&o, 4096);
     // OCC = 1: pad the allocation past half the LDS so that ONE workgroup is resident per CU whatever the register count is
-    const size_t lds = (size_t)H3D_RING_DEPTH * NT * 2048 + (OCC == 1 ? 48 * 1024 : 0);
+    const size_t lds = (size_t)kWeightRingDepth * NT * 2048 + (OCC == 1 ? 48 * 1024 : 0);
     hipFuncSetAttribute(reinterpret_cast<const void*>(probe), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     int nb = 0; hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, probe, 256, lds);
     hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);

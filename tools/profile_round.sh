@@ -1,8 +1,9 @@
 #!/bin/bash
-# Round profile: bench line, rocprofv3 kernel stats of the same command, separate PMC passes for HBM traffic and for the SQ
-# counters, the same for the wide (x3t) workload.  usage (on the GPU box, from the repo root):  bash tools/profile_round.sh r2
+# Profile of the tree: bench line, rocprofv3 kernel stats of the same command, separate PMC passes for HBM traffic and for the SQ
+# counters, the same for the wide (x3t) workload, config 4's training lines with kernel tables, the one-rank RCCL lines.
+# usage (on the GPU box, from the repo root):  bash tools/profile_round.sh [tag]
 set -u
-R=${1:-r5}
+R=${1:-profile}
 OUT=$PWD/gpurun_out/$R
 mkdir -p $OUT
 REPO=$PWD
@@ -27,7 +28,8 @@ python tools/rocprof_summary.py $(find $OUT/stats_wide -name '*.db' | head -1) $
 for c in FETCH_SIZE WRITE_SIZE sq1 sq2 wide; do
   python tools/pmc_dump.py $(find $OUT/pmc_$c -name '*.db' | head -1) "$KERN" > $OUT/pmc_$c.txt
 done
-python tools/traffic_json.py $OUT/pmc_FETCH_SIZE.txt $OUT/pmc_WRITE_SIZE.txt MAP3DBN512_512x512_b16_s64 $OUT/hbm_traffic.json
+SCLK=$(python -c "import json; print(json.load(open('$OUT/bench_detail.json'))['telemetry']['timed']['gfxclk_MHz']['median'])" 2>/dev/null || echo 2100)
+python tools/traffic_json.py $OUT/pmc_FETCH_SIZE.txt $OUT/pmc_WRITE_SIZE.txt MAP3DBN512_512x512_b16_s64 $OUT/hbm_traffic.json $OUT/pmc_sq2.txt $OUT/kernel_stats.csv $SCLK > /dev/null
 # BASELINE config 4: one adversarial iteration per step (MIOpen's search results come from tools/miopen_db)
 python bench.py --mode trainstep --batch 4 --steps 5 --warmup 2 > $OUT/trainstep_1gpu.json 2> $OUT/trainstep.err
 python tools/train_profile.py 4 g > $OUT/trainstep_gstep_kernels.txt 2>> $OUT/trainstep.err
@@ -41,5 +43,8 @@ cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/stats_train_amp -o k -- python $REPO/bench.py --mode trainstep --batch 4 --steps 3 --warmup 6 --amp fp16 > /dev/null 2>> $OUT/trainstep.err
 cd $REPO
 python tools/rocprof_summary.py $(find $OUT/stats_train_amp -name '*.db' | head -1) $OUT/trainstep_amp_fp16_kernel_stats.csv
+# one-rank RCCL lines: the driver's N > 1 command line with one rank (process group over RCCL, barrier, MAX all-reduce of the time)
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --steps 10 --warmup 3 --no-extra --no-cpu --check-items 2 > $OUT/bench_torchrun_1rank_rccl.json 2> $OUT/torchrun.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 1 --mode trainstep --batch 4 --steps 3 --warmup 2 > $OUT/trainstep_torchrun_1rank_rccl.json 2>> $OUT/torchrun.err
 find $OUT -name '*.db' -delete
-tail -c 400 $OUT/bench.json
+tail -c 600 $OUT/bench.json; echo; tail -c 300 $OUT/bench_torchrun_1rank_rccl.json; echo; tail -c 300 $OUT/trainstep_torchrun_1rank_rccl.json
