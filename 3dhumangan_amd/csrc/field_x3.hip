@@ -33,6 +33,7 @@
 // input layers (K = 3 / 31 / view direction) and the 1-row heads stay on three f16 products.  Error model and budget:
 // tests/x2_emulation.py, tests/test_x2_error_model_cpu.py (2e-5 at the operator boundary at width 256).
 #include "x3_common.hpp"
+#include "field_pack.hpp"
 #include <string.h>
 #include <math.h>
 #include <stdio.h>
@@ -184,7 +185,7 @@ __device__ __forceinline__ void split8(const float (&v)[8], float scale, half8& 
 
 // K order of every GEMM that consumes accumulators ("acc order"): the accumulator registers a lane holds for tile t ARE
 // its B-fragment elements -- register r = 8j + e of tile t is element e of k-step 2t + j -- so no cross-lane relayout is
-// needed; the host packs the weights' K dimension accordingly (k_of below / acc_k in the packer):
+// needed; the host packs the weights' K dimension accordingly (field_pack.hpp: acc_k):
 //     feature of k-slot (h, e) of k-step ks:  32*(ks/2) + (e & 3) + 8*(2*(ks & 1) + (e >> 2)) + 4*h
 __device__ __forceinline__ void set_word(half8& f, int w, unsigned v) {
     u32x4 t = __builtin_bit_cast(u32x4, f);
@@ -847,277 +848,54 @@ int launch(const Args& A, int B, int64_t groups, hipStream_t st) {
     }
 }
 
-// ---------------------------------------------------------------- host-side packing
+// ---------------------------------------------------------------- weight packing
+// The blob is described ONCE, as a table of matrices (make_pack_args: which slice of which parameter, in which K order, under the
+// scale of which slice, with which inv_scale slot) plus a tail (biases, the four head rows).  Two packers walk that description
+// with the same __host__ __device__ code (field_pack.hpp for the arithmetic; pack_job / pack_tail below for where the bytes go):
+// the CPU in h3d_field_pack_x3 / _x2, and field_pack_kernel in h3d_field_pack_x3_device / _x2_device for parameters that live on
+// the DEVICE -- weights that change every optimiser step (the D step's no-grad generator forward, reference
+// lib/trainers/phase_trainer.py:355-362) reach the fused render without a D2H copy, host pack and H2D copy (~10 ms and a
+// stream synchronisation per weight version).  The blobs are bit-identical (tests/test_gpu_field_pack_device.py).
 
-__host__ __device__ inline uint16_t f32_to_f16_rn(float f) {            // round-to-nearest-even, handles subnormals; inputs are finite
-    uint32_t x;
-    memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    x &= 0x7fffffffu;
-    if (x >= 0x47800000u) return (uint16_t)(sign | 0x7bffu);          // clamp to max finite (never hit: scaled)
-    if (x < 0x38800000u) {                                             // subnormal / zero in f16
-        if (x < 0x33000000u) return (uint16_t)sign;
-        const uint32_t mant = (x & 0x7fffffu) | 0x800000u;
-        const int shift = 126 - (int)(x >> 23);                       // 14..24
-        uint32_t r = mant >> shift;
-        const uint32_t rem = mant & ((1u << shift) - 1), half = 1u << (shift - 1);
-        if (rem > half || (rem == half && (r & 1))) ++r;
-        return (uint16_t)(sign | r);
-    }
-    uint32_t r = ((x - 0x38000000u) >> 13);
-    const uint32_t rem = x & 0x1fffu;
-    if (rem > 0x1000u || (rem == 0x1000u && (r & 1))) ++r;
-    return (uint16_t)(sign | r);
-}
+constexpr float kScaleTarget = 8192.f;         // every matrix is scaled by the largest power of two that keeps |w| * scale <= 2^13
 
-__host__ __device__ inline float f16_to_f32(uint16_t v) {
-    const uint32_t sign = (uint32_t)(v & 0x8000u) << 16;
-    uint32_t e = (v >> 10) & 0x1f, m = v & 0x3ffu, x;
-    if (e == 0) {
-        if (m == 0) x = sign;
-        else {
-            int s = 0;
-            while (!(m & 0x400u)) { m <<= 1; ++s; }
-            x = sign | ((uint32_t)(113 - s) << 23) | ((m & 0x3ffu) << 13);
-        }
-    } else x = sign | ((e + 112) << 23) | (m << 13);
-    float f;
-    memcpy(&f, &x, 4);
-    return f;
-}
-
-// floor(log2(q)) of a positive finite q, from the exponent field (exact; log2f may round up to the next integer just below a
-// power of two, and host and device must agree bit for bit: h3d_field_pack_*_device)
-__host__ __device__ inline int floor_log2(float q) {
-    uint32_t x;
-    memcpy(&x, &q, 4);
-    const int e = (int)((x >> 23) & 0xffu);
-    if (e) return e - 127;
-    int s = 0;                                   // subnormal
-    for (uint32_t m = x & 0x7fffffu; m && !(m & 0x400000u); m <<= 1) ++s;
-    return -127 - s;
-}
-// the largest power of two 2^e with mx * 2^e <= target (1 for an all-zero matrix)
-__host__ __device__ inline float pow2_scale_of(float mx, float target) { return mx > 0.f ? ldexpf(1.f, floor_log2(target / mx)) : 1.f; }
-
-float pow2_scale(const float* w, int64_t n, float target) {
-    float mx = 0.f;
-    for (int64_t i = 0; i < n; ++i) mx = fmaxf(mx, fabsf(w[i]));
-    return pow2_scale_of(mx, target);
-}
-
-// input feature of k-slot (half hh, element e) of k-step ks when the consumer's B fragments are accumulator registers
-// (see FilmProducer): tile ks/2, accumulator register r = 8*(ks & 1) + e  ->  row (r & 3) + 8*(r >> 2) + 4*hh
-__host__ __device__ inline int acc_k(int ks, int hh, int e) { return 32 * (ks / 2) + (e & 3) + 8 * (2 * (ks & 1) + (e >> 2)) + 4 * hh; }
-
-// W [n_out, ld] row-major; K range [in_begin, in_begin+in_count) -> [KSm][NT][2][64][8] f16, scaled by `scale`.
-// acc_order: K runs in accumulator-register order (the input comes from a previous layer's accumulators) instead of
-// the natural order (inputs assembled from memory: coordinates, geometry features, view direction).
-__host__ __device__ inline void pack_x3_unit(const float* w, int ld, int in_begin, int in_count, int n_out, int NT, float scale,
-                                             uint16_t* dst, bool acc_order, int ks, int nt, int lane) {
+// lane `lane` of (k-step ks, tile nt) of a matrix [KSm][NT][hi | lo][64][8] f16, scaled by `scale`
+__host__ __device__ inline void pack_x3_unit(const WeightSlice& m, int NT, float scale, uint16_t* dst, bool acc_order, int ks, int nt, int lane) {
+    const int64_t base = (((int64_t)ks * NT + nt) * 2) * 64 * 8 + lane * 8;
     for (int e = 0; e < 8; ++e) {
-        const int k = acc_order ? acc_k(ks, lane >> 5, e) : 16 * ks + 8 * (lane >> 5) + e, nn = 32 * nt + (lane & 31);
-        float v = 0.f;
-        if (k < in_count && nn < n_out) v = w[(int64_t)nn * ld + in_begin + k] * scale;
-        const uint16_t hi = f32_to_f16_rn(v);
-        const uint16_t lo = f32_to_f16_rn(v - f16_to_f32(hi));
-        const int64_t base = (((int64_t)ks * NT + nt) * 2) * 64 * 8;
-        dst[base + lane * 8 + e] = hi;
-        dst[base + 64 * 8 + lane * 8 + e] = lo;
+        uint16_t hi, lo;
+        split_f16(m.at(32 * nt + (lane & 31), slot_k(acc_order, ks, lane >> 5, e), scale), hi, lo);
+        dst[base + e] = hi;
+        dst[base + 64 * 8 + e] = lo;
     }
 }
-void pack_x3(const float* w, int ld, int in_begin, int in_count, int n_out, int KSm, int NT, float scale, uint16_t* dst,
-             bool acc_order) {
-    for (int ks = 0; ks < KSm; ++ks)
-        for (int nt = 0; nt < NT; ++nt)
-            for (int lane = 0; lane < 64; ++lane) pack_x3_unit(w, ld, in_begin, in_count, n_out, NT, scale, dst, acc_order, ks, nt, lane);
-}
 
-// ---- x2 packing: fp6 (e2m3) codes and block scales
-__host__ __device__ inline float e2m3_value(unsigned c) {
-    const int e = (c >> 3) & 3, m = c & 7;
-    const float r = e ? ldexpf(1.f + m / 8.f, e - 1) : m / 8.f;
-    return (c & 32) ? -r : r;
-}
-__host__ __device__ inline unsigned e2m3_code(float v) {            // round-to-nearest-even on the code grid, saturating at 7.5
-    const unsigned sign = v < 0.f ? 32u : 0u;
-    const float a = fminf(fabsf(v), 7.5f);
-    const float step = a < 2.f ? 0.125f : a < 4.f ? 0.25f : 0.5f;
-    const float q = nearbyintf(a / step) * step;         // default rounding mode: ties to even; spacing doubles exactly at 2 and 4
-    unsigned c;
-    if (q < 2.f) c = (unsigned)(q * 8.f);                // 0 .. 15: subnormals 0..7 and [1, 2)
-    else if (q < 4.f) c = 16u + (unsigned)((q - 2.f) * 4.f);
-    else c = 24u + (unsigned)((q - 4.f) * 2.f);
-    return sign | c;
-}
-
-// W [n_out, ld] row-major; K range [in_begin, in_begin + in_count) in accumulator order over KSm (even) k-steps ->
+// lane `lane` of (K-tile T, tile nt) of an accumulator-order matrix over KSm (even) k-steps in the x2 arithmetic ->
 // stages [KSm][NT][hi fragment 1 KiB | fp6 half-record 1 KiB], weights scaled by `scale` (the f16 scale of the matrix);
 // the destination must be zero-initialised (the odd stages' half-records end in 256 B of padding)
-__host__ __device__ inline void pack_x2_unit(const float* w, int ld, int in_begin, int in_count, int n_out, int NT, float scale,
-                                             unsigned char* dst, int T, int nt, int lane) {
-    const int nn = 32 * nt + (lane & 31), hh = lane >> 5;
-    float hi[16], lo[16], mx = 0.f;
+__host__ __device__ inline void pack_x2_unit(const WeightSlice& m, int NT, float scale, unsigned char* dst, int T, int nt, int lane) {
+    uint16_t h16[16];
+    unsigned rec[8];
+    x2_lane_tile(m, scale, 32 * nt + (lane & 31), lane >> 5, T, h16, rec);
+    auto stage = [&](int j, int half) { return dst + (((int64_t)(2 * T + j) * NT + nt) * 2 + half) * 1024; };
     for (int j = 0; j < 2; ++j)
-        for (int e = 0; e < 8; ++e) {
-            const int k = acc_k(2 * T + j, hh, e);
-            float v = 0.f;
-            if (k < in_count && nn < n_out) v = w[(int64_t)nn * ld + in_begin + k] * scale;
-            const uint16_t h16 = f32_to_f16_rn(v);
-            hi[8 * j + e] = f16_to_f32(h16);
-            lo[8 * j + e] = v - hi[8 * j + e];
-            mx = fmaxf(mx, fabsf(hi[8 * j + e]));
-            uint16_t* hd = reinterpret_cast<uint16_t*>(dst + (((int64_t)(2 * T + j) * NT + nt) * 2) * 1024);
-            hd[lane * 8 + e] = h16;
-        }
-    // block scale alpha = 2^ea: the largest with |hi| * alpha <= 7.5 unless a lo code would saturate (then half of
-    // it); the instruction multiplies the codes by 2^(byte - 127) = 1 / alpha
-    int ea = mx > 0.f ? floor_log2(7.5f / mx) : 0;
-    if (ea > 100) ea = 100;
-    if (ea < -100) ea = -100;
-    // (f16-subnormal hi values leave lo up to 2^-1 of hi instead of 2^-11: several steps then)
-    for (bool sat = true; sat && ea > -100;) {
-        sat = false;
-        for (int i = 0; i < 16; ++i) sat = sat || fabsf(lo[i]) * kX2Rho * ldexpf(1.f, ea) > 7.5f;
-        if (sat) --ea;
-    }
-    const float alpha = ldexpf(1.f, ea);
-    unsigned rec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int sl = 0; sl < 32; ++sl) {
-        const float v = sl < 16 ? hi[sl] * alpha : lo[sl - 16] * alpha * kX2Rho;
-        const uint64_t code = e2m3_code(v);
-        const int bit = 6 * sl;
-        rec[bit / 32] |= (unsigned)(code << (bit & 31));
-        if ((bit & 31) > 26) rec[bit / 32 + 1] |= (unsigned)(code >> (32 - (bit & 31)));
-    }
-    rec[6] = (unsigned)(127 - ea) * 0x01010101u;
+        for (int e = 0; e < 8; ++e) reinterpret_cast<uint16_t*>(stage(j, 0))[lane * 8 + e] = h16[8 * j + e];
     // even stage: code dwords 0-3, 16 B per lane; odd stage: code dwords 4-5 as [64 lanes][8 B], then the scale dwords as
     // [64 lanes][4 B], then 256 B of zeros -- dense, so that gemm_x2_roll's 64- and 32-bit reads are bank-conflict-free
-    unsigned* ev = reinterpret_cast<unsigned*>(dst + (((int64_t)(2 * T) * NT + nt) * 2 + 1) * 1024);
-    unsigned* od = reinterpret_cast<unsigned*>(dst + (((int64_t)(2 * T + 1) * NT + nt) * 2 + 1) * 1024);
+    unsigned* ev = reinterpret_cast<unsigned*>(stage(0, 1));
+    unsigned* od = reinterpret_cast<unsigned*>(stage(1, 1));
     for (int d = 0; d < 4; ++d) ev[lane * 4 + d] = rec[d];
     od[lane * 2 + 0] = rec[4];
     od[lane * 2 + 1] = rec[5];
     od[128 + lane] = rec[6];
 }
-void pack_x2(const float* w, int ld, int in_begin, int in_count, int n_out, int KSm, int NT, float scale, unsigned char* dst) {
-    for (int T = 0; T < KSm / 2; ++T)
-        for (int nt = 0; nt < NT; ++nt)
-            for (int lane = 0; lane < 64; ++lane) pack_x2_unit(w, ld, in_begin, in_count, n_out, NT, scale, dst, T, nt, lane);
-}
-
-}  // namespace
-
-extern "C" int h3d_field_x3_layout(int Hd, int F, int64_t* out, int n_out) {
-    H3D_REQUIRE(out && n_out >= 20, "h3d_field_x3_layout: need room for 20 values");
-    H3D_REQUIRE(Hd >= 1 && F >= 1 && Hd <= 256 && F <= 256, "h3d_field_x3_layout: widths up to 256 (got %d, %d)", Hd, F);
-    const LayoutX3 L = make_layout(Hd, F);
-    int i = 0;
-    out[i++] = L.NT; out[i++] = L.KS; out[i++] = L.HdP; out[i++] = L.stages;
-    for (int w = 0; w < W_COUNT; ++w) out[i++] = L.w[w];
-    out[i++] = L.inv_scale; out[i++] = L.bias; out[i++] = L.b_feat; out[i++] = L.head_w; out[i++] = L.head_inv;
-    out[i++] = L.head_b; out[i++] = L.total;
-    return H3D_OK;
-}
-
-extern "C" int64_t h3d_field_pack_x3_size(int Hd, int F) {
-    if (Hd < 1 || F < 1 || Hd > 256 || F > 256) return -1;
-    return make_layout(Hd, F).total;
-}
-
-static int field_pack(const h3d_field_params* p, int Hd, int F, void* blob_, bool x2) {
-    H3D_REQUIRE(p && blob_, "h3d_field_pack_x3 / _x2: null pointer");
-    H3D_REQUIRE(Hd >= 1 && F >= 1 && Hd <= 256 && F <= 256, "h3d_field_pack_x3 / _x2: widths up to 256 (got %d, %d)", Hd, F);
-    const LayoutX3 L = make_layout(Hd, F, x2);
-    unsigned char* blob = static_cast<unsigned char*>(blob_);
-    memset(blob, 0, L.total);
-    float* invs = reinterpret_cast<float*>(blob + L.inv_scale);
-    const float target = 8192.f;
-    auto mat = [&](int wi, const float* w, int ld, int in_begin, int in_count, int n_out, int KSm, float in_scale, bool acc_order) {
-        // scale taken over the slice actually used
-        float mx = 0.f;
-        for (int nn = 0; nn < n_out; ++nn)
-            for (int k = 0; k < in_count; ++k) mx = fmaxf(mx, fabsf(w[(int64_t)nn * ld + in_begin + k]));
-        const float sc = pow2_scale_of(mx, target);
-        if (x2 && acc_order) pack_x2(w, ld, in_begin, in_count, n_out, KSm, L.NT, sc, blob + L.w[wi]);
-        else pack_x3(w, ld, in_begin, in_count, n_out, KSm, L.NT, sc, reinterpret_cast<uint16_t*>(blob + L.w[wi]), acc_order);
-        invs[wi] = 1.f / (sc * in_scale);
-        return sc;
-    };
-    mat(W_COORD, p->w_coord, 3, 0, 3, Hd, 1, kSIn, false);
-    mat(W_GEO, p->w_geo, 31, 0, 31, Hd, 2, kSIn, false);
-    // FiLM 0: both halves must share one scale because they accumulate into the same registers
-    {
-        const float sc = pow2_scale(p->w_film[0], (int64_t)Hd * 2 * Hd, target);
-        if (x2) {
-            pack_x2(p->w_film[0], 2 * Hd, 0, Hd, Hd, L.KS, L.NT, sc, blob + L.w[W_F0A]);
-            pack_x2(p->w_film[0], 2 * Hd, Hd, Hd, Hd, L.KS, L.NT, sc, blob + L.w[W_F0B]);
-        } else {
-            pack_x3(p->w_film[0], 2 * Hd, 0, Hd, Hd, L.KS, L.NT, sc, reinterpret_cast<uint16_t*>(blob + L.w[W_F0A]), true);
-            pack_x3(p->w_film[0], 2 * Hd, Hd, Hd, Hd, L.KS, L.NT, sc, reinterpret_cast<uint16_t*>(blob + L.w[W_F0B]), true);
-        }
-        invs[W_F0A] = invs[W_F0B] = 1.f / (sc * kSA);
-    }
-    for (int l = 1; l < 4; ++l) mat(W_F1 + l - 1, p->w_film[l], Hd, 0, Hd, Hd, L.KS, kSA, true);
-    // colour layer: KS k-steps over the hidden features (columns 3..) + one k-step over the view direction (columns 0..2),
-    // one scale for the whole matrix (same accumulators)
-    {
-        const float sc = pow2_scale(p->w_color, (int64_t)Hd * (Hd + 3), target);
-        uint16_t* dst = reinterpret_cast<uint16_t*>(blob + L.w[W_COLOR]);
-        if (x2) pack_x2(p->w_color, Hd + 3, 3, Hd, Hd, L.KS, L.NT, sc, blob + L.w[W_COLOR]);
-        else pack_x3(p->w_color, Hd + 3, 3, Hd, Hd, L.KS, L.NT, sc, dst, true);
-        pack_x3(p->w_color, Hd + 3, 0, 3, Hd, 1, L.NT, sc, dst + (int64_t)L.KS * L.NT * 2 * 64 * 8, false);
-        invs[W_COLOR] = 1.f / (sc * kSA);
-    }
-    mat(W_FEAT, p->w_feat, Hd, 0, Hd, F, L.KS, kSA, true);
-    float* bias = reinterpret_cast<float*>(blob + L.bias);
-    for (int nn = 0; nn < Hd; ++nn) {
-        bias[ST_GEO * L.HdP + nn] = p->b_geo[nn];
-        bias[ST_COORD * L.HdP + nn] = p->b_coord[nn];
-        for (int l = 0; l < 4; ++l) bias[(ST_FILM0 + l) * L.HdP + nn] = p->b_film[l][nn];
-        bias[ST_COLOR * L.HdP + nn] = p->b_color[nn];
-    }
-    float* bf = reinterpret_cast<float*>(blob + L.b_feat);
-    for (int nn = 0; nn < F; ++nn) bf[nn] = p->b_feat[nn];
-    // heads: [head][hi / lo (/ hi * 2^-12)][ks][half][8]
-    const int PL = L.head_planes;
-    uint16_t* hw = reinterpret_cast<uint16_t*>(blob + L.head_w);
-    float* hinv = reinterpret_cast<float*>(blob + L.head_inv);
-    float* hb = reinterpret_cast<float*>(blob + L.head_b);
-    for (int hd = 0; hd < 4; ++hd) {
-        const float* w = hd == 0 ? p->w_sigma : p->w_rgb + (int64_t)(hd - 1) * Hd;
-        const float sc = pow2_scale(w, Hd, target);
-        for (int ks = 0; ks < L.KS; ++ks)
-            for (int hh = 0; hh < 2; ++hh)
-                for (int e = 0; e < 8; ++e) {
-                    const int k = acc_k(ks, hh, e);
-                    const float v = k < Hd ? w[k] * sc : 0.f;
-                    const uint16_t hi = f32_to_f16_rn(v), lo = f32_to_f16_rn(v - f16_to_f32(hi));
-                    hw[((((int64_t)hd * PL + 0) * L.KS + ks) * 2 + hh) * 8 + e] = hi;
-                    hw[((((int64_t)hd * PL + 1) * L.KS + ks) * 2 + hh) * 8 + e] = lo;
-                    if (x2) hw[((((int64_t)hd * PL + 2) * L.KS + ks) * 2 + hh) * 8 + e] = f32_to_f16_rn(f16_to_f32(hi) / kX2Rho);
-                }
-        hinv[hd] = 1.f / (sc * kSA);
-        hb[hd] = hd == 0 ? p->b_sigma[0] : p->b_rgb[hd - 1];
-    }
-    return H3D_OK;
-}
-
-
-// ---------------------------------------------------------------- device-side packing (round 6)
-// The same blob from parameters that live on the DEVICE, in one launch: weights that change every optimiser step (the D step's
-// no-grad generator forward, /root/reference/lib/trainers/phase_trainer.py:355-362) reach the fused render without the D2H copy,
-// host pack and H2D copy of field_pack (~10 ms and a stream synchronisation per weight version).  The arithmetic is the host
-// packer's own (pack_x3_unit / pack_x2_unit / pow2_scale_of are __host__ __device__; every operation in them is exact or an
-// IEEE-rounded division), so the blobs are bit-identical (tests/test_gpu_field_pack_device.py).
-namespace {
 
 struct PackJob {
-    const float* w;                       // matrix to pack (rows of `ld` floats)
-    int ld, in_begin, in_count, n_out, KSm;
+    WeightSlice m;                        // the matrix to pack
+    int KSm;                              // k-steps
     int kind;                             // 0: x3, natural K order; 1: x3, accumulator K order; 2: x2 (accumulator order)
     int64_t dst;                          // byte offset of the matrix in the blob
-    int s_rows, s_ld, s_begin, s_count;   // the slice of `w` the scale is taken over (rows x columns)
+    int s_rows, s_count;                  // the scale is taken over rows [0, s_rows) x columns [0, s_count) of m.w
     int inv_slot;                         // index into inv_scale[] (or -1)
     float in_scale;
 };
@@ -1129,6 +907,92 @@ struct PackArgs {
     unsigned char* blob;
     int Hd, F, x2;
 };
+
+PackArgs make_pack_args(const h3d_field_params* p, int Hd, int F, void* blob, bool x2) {
+    PackArgs A{};
+    A.L = make_layout(Hd, F, x2);
+    A.p = *p; A.blob = static_cast<unsigned char*>(blob); A.Hd = Hd; A.F = F; A.x2 = x2 ? 1 : 0;
+    const LayoutX3& L = A.L;
+    int n = 0;
+    auto job = [&](int64_t dst, const float* w, int ld, int in_begin, int in_count, int n_out, int KSm, int kind, int s_rows, int s_count,
+                   int inv_slot, float in_scale) {
+        A.job[n++] = PackJob{{w, ld, in_begin, in_count, n_out}, KSm, kind, dst, s_rows, s_count, inv_slot, in_scale};
+    };
+    const int acc = x2 ? 2 : 1;
+    job(L.w[W_COORD], p->w_coord, 3, 0, 3, Hd, 1, 0, Hd, 3, W_COORD, kSIn);
+    job(L.w[W_GEO], p->w_geo, 31, 0, 31, Hd, 2, 0, Hd, 31, W_GEO, kSIn);
+    job(L.w[W_F0A], p->w_film[0], 2 * Hd, 0, Hd, Hd, L.KS, acc, Hd, 2 * Hd, W_F0A, kSA);      // both halves: one scale (same accumulators)
+    job(L.w[W_F0B], p->w_film[0], 2 * Hd, Hd, Hd, Hd, L.KS, acc, Hd, 2 * Hd, W_F0B, kSA);
+    for (int l = 1; l < 4; ++l) job(L.w[W_F1 + l - 1], p->w_film[l], Hd, 0, Hd, Hd, L.KS, acc, Hd, Hd, W_F1 + l - 1, kSA);
+    // colour layer: KS k-steps over the hidden features (columns 3..) + one k-step over the view direction (columns 0..2, natural
+    // order), one scale for the whole matrix (same accumulators)
+    job(L.w[W_COLOR], p->w_color, Hd + 3, 3, Hd, Hd, L.KS, acc, Hd, Hd + 3, W_COLOR, kSA);
+    job(L.w[W_COLOR] + (int64_t)L.KS * L.NT * 2 * 64 * 8 * 2, p->w_color, Hd + 3, 0, 3, Hd, 1, 0, Hd, Hd + 3, -1, kSA);
+    job(L.w[W_FEAT], p->w_feat, Hd, 0, Hd, F, L.KS, acc, F, Hd, W_FEAT, kSA);      // (the table has kPackJobs rows)
+    return A;
+}
+
+// The packers below are written for a team of `stride` workers of which the caller is number `first`; max_of(v) returns the
+// maximum of the workers' v.  The CPU is a team of one (first 0, stride 1, max_of the identity), a workgroup a team of 256.
+
+// One matrix: its scale and inv_scale slot, then share `part` of `parts` of its units (a unit = one lane of one tile and k-step).
+template <typename MAX>
+__host__ __device__ inline void pack_job(const PackJob& J, const LayoutX3& L, unsigned char* blob, int first, int stride, int part, int parts,
+                                         MAX max_of) {
+    float mx = 0.f;
+    for (int i = first; i < J.s_rows * J.s_count; i += stride) {
+        const int r = i / J.s_count, c = i - r * J.s_count;
+        mx = fmaxf(mx, fabsf(J.m.w[(int64_t)r * J.m.ld + c]));
+    }
+    const float sc = pow2_scale_of(max_of(mx), kScaleTarget);
+    if (first == 0 && part == 0 && J.inv_slot >= 0) reinterpret_cast<float*>(blob + L.inv_scale)[J.inv_slot] = 1.f / (sc * J.in_scale);
+    const int rows = J.kind == 2 ? J.KSm / 2 : J.KSm;               // k-steps (x3) or k-step pairs (x2)
+    const int units = rows * L.NT * 64;
+    for (int u = part * stride + first; u < units; u += parts * stride) {
+        const int lane = u & 63, nt = (u >> 6) % L.NT, r = (u >> 6) / L.NT;
+        if (J.kind == 2) pack_x2_unit(J.m, L.NT, sc, blob + J.dst, r, nt, lane);
+        else pack_x3_unit(J.m, L.NT, sc, reinterpret_cast<uint16_t*>(blob + J.dst), J.kind == 1, r, nt, lane);
+    }
+}
+
+// Biases, b_feat and the four head rows [head][hi / lo (/ hi * 2^-12: x2)][ks][half][8], each head under its own scale.
+template <typename MAX>
+__host__ __device__ inline void pack_tail(const PackArgs& A, int first, int stride, MAX max_of) {
+    const LayoutX3& L = A.L;
+    const h3d_field_params& p = A.p;
+    float* bias = reinterpret_cast<float*>(A.blob + L.bias);
+    for (int nn = first; nn < A.Hd; nn += stride) {
+        bias[ST_GEO * L.HdP + nn] = p.b_geo[nn];
+        bias[ST_COORD * L.HdP + nn] = p.b_coord[nn];
+        for (int l = 0; l < 4; ++l) bias[(ST_FILM0 + l) * L.HdP + nn] = p.b_film[l][nn];
+        bias[ST_COLOR * L.HdP + nn] = p.b_color[nn];
+    }
+    float* bf = reinterpret_cast<float*>(A.blob + L.b_feat);
+    for (int nn = first; nn < A.F; nn += stride) bf[nn] = p.b_feat[nn];
+    uint16_t* hw = reinterpret_cast<uint16_t*>(A.blob + L.head_w);
+    float* hinv = reinterpret_cast<float*>(A.blob + L.head_inv);
+    float* hb = reinterpret_cast<float*>(A.blob + L.head_b);
+    const int plane = L.KS * 16;                                    // f16 values per plane of a head
+    for (int hd = 0; hd < 4; ++hd) {
+        const float* w = hd == 0 ? p.w_sigma : p.w_rgb + (int64_t)(hd - 1) * A.Hd;
+        float mx = 0.f;
+        for (int k = first; k < A.Hd; k += stride) mx = fmaxf(mx, fabsf(w[k]));
+        const float sc = pow2_scale_of(max_of(mx), kScaleTarget);
+        for (int u = first; u < plane; u += stride) {               // u = (ks, half, e)
+            const int k = acc_k(u >> 4, (u >> 3) & 1, u & 7);
+            uint16_t hi, lo;
+            split_f16(k < A.Hd ? w[k] * sc : 0.f, hi, lo);
+            uint16_t* q = hw + (int64_t)hd * L.head_planes * plane + u;
+            q[0] = hi;
+            q[plane] = lo;
+            if (A.x2) q[2 * plane] = f32_to_f16_rn(f16_to_f32(hi) / kX2Rho);
+        }
+        if (first == 0) {
+            hinv[hd] = 1.f / (sc * kSA);
+            hb[hd] = hd == 0 ? p.b_sigma[0] : p.b_rgb[hd - 1];
+        }
+    }
+}
 
 __device__ inline float block_max(float v, float* red) {       // 256 threads; every thread returns the maximum
     const int t = threadIdx.x;
@@ -1143,125 +1007,75 @@ __device__ inline float block_max(float v, float* red) {       // 256 threads; e
     return m;
 }
 
+// grid (kPackJobs + 1, kPackSplit): every workgroup of a matrix takes the scale itself (<= 66 k values from the L2) and packs its
+// share of the units; the last column's first workgroup packs the tail
 __global__ __launch_bounds__(256) void field_pack_kernel(PackArgs A) {
     __shared__ float red[256];
     const int t = threadIdx.x;
-    const float target = 8192.f;
-    const LayoutX3& L = A.L;
-    unsigned char* blob = A.blob;
+    auto wg_max = [&](float v) { return block_max(v, red); };
     if ((int)blockIdx.x == kPackJobs) {
-        // biases and the four heads (one workgroup)
-        if (blockIdx.y) return;
-        float* bias = reinterpret_cast<float*>(blob + L.bias);
-        for (int nn = t; nn < A.Hd; nn += 256) {
-            bias[ST_GEO * L.HdP + nn] = A.p.b_geo[nn];
-            bias[ST_COORD * L.HdP + nn] = A.p.b_coord[nn];
-            for (int l = 0; l < 4; ++l) bias[(ST_FILM0 + l) * L.HdP + nn] = A.p.b_film[l][nn];
-            bias[ST_COLOR * L.HdP + nn] = A.p.b_color[nn];
-        }
-        float* bf = reinterpret_cast<float*>(blob + L.b_feat);
-        for (int nn = t; nn < A.F; nn += 256) bf[nn] = A.p.b_feat[nn];
-        const int PL = L.head_planes;
-        uint16_t* hw = reinterpret_cast<uint16_t*>(blob + L.head_w);
-        float* hinv = reinterpret_cast<float*>(blob + L.head_inv);
-        float* hb = reinterpret_cast<float*>(blob + L.head_b);
-        for (int hd = 0; hd < 4; ++hd) {
-            const float* w = hd == 0 ? A.p.w_sigma : A.p.w_rgb + (int64_t)(hd - 1) * A.Hd;
-            float mx = 0.f;
-            for (int k = t; k < A.Hd; k += 256) mx = fmaxf(mx, fabsf(w[k]));
-            const float sc = pow2_scale_of(block_max(mx, red), target);
-            for (int u = t; u < L.KS * 16; u += 256) {
-                const int ks = u >> 4, hh = (u >> 3) & 1, e = u & 7;
-                const int k = acc_k(ks, hh, e);
-                const float v = k < A.Hd ? w[k] * sc : 0.f;
-                const uint16_t hi = f32_to_f16_rn(v), lo = f32_to_f16_rn(v - f16_to_f32(hi));
-                hw[((((int64_t)hd * PL + 0) * L.KS + ks) * 2 + hh) * 8 + e] = hi;
-                hw[((((int64_t)hd * PL + 1) * L.KS + ks) * 2 + hh) * 8 + e] = lo;
-                if (A.x2) hw[((((int64_t)hd * PL + 2) * L.KS + ks) * 2 + hh) * 8 + e] = f32_to_f16_rn(f16_to_f32(hi) / kX2Rho);
-            }
-            if (t == 0) {
-                hinv[hd] = 1.f / (sc * kSA);
-                hb[hd] = hd == 0 ? A.p.b_sigma[0] : A.p.b_rgb[hd - 1];
-            }
-        }
+        if (blockIdx.y == 0) pack_tail(A, t, 256, wg_max);
         return;
     }
-    const PackJob& J = A.job[blockIdx.x];
-    // every workgroup of a matrix takes the scale itself (<= 66 k values from the L2) and packs its share of the units
-    float mx = 0.f;
-    for (int i = t; i < J.s_rows * J.s_count; i += 256) {
-        const int r = i / J.s_count, c = i - r * J.s_count;
-        mx = fmaxf(mx, fabsf(J.w[(int64_t)r * J.s_ld + J.s_begin + c]));
-    }
-    const float sc = pow2_scale_of(block_max(mx, red), target);
-    if (t == 0 && blockIdx.y == 0 && J.inv_slot >= 0) reinterpret_cast<float*>(blob + L.inv_scale)[J.inv_slot] = 1.f / (sc * J.in_scale);
-    const int rows = J.kind == 2 ? J.KSm / 2 : J.KSm;               // k-steps (x3) or k-step pairs (x2)
-    const int units = rows * L.NT * 64;
-    for (int u = (int)blockIdx.y * 256 + t; u < units; u += kPackSplit * 256) {
-        const int lane = u & 63, nt = (u >> 6) % L.NT, r = (u >> 6) / L.NT;
-        if (J.kind == 2) pack_x2_unit(J.w, J.ld, J.in_begin, J.in_count, J.n_out, L.NT, sc, blob + J.dst, r, nt, lane);
-        else pack_x3_unit(J.w, J.ld, J.in_begin, J.in_count, J.n_out, L.NT, sc, reinterpret_cast<uint16_t*>(blob + J.dst), J.kind == 1, r, nt, lane);
-    }
+    pack_job(A.job[blockIdx.x], A.L, A.blob, t, 256, (int)blockIdx.y, kPackSplit, wg_max);
 }
 
-int field_pack_device(const h3d_field_params* p, int Hd, int F, void* blob_, bool x2, h3d_stream_t stream) {
-    H3D_REQUIRE(p && blob_, "h3d_field_pack_x3_device / _x2_device: null pointer");
-    H3D_REQUIRE(Hd >= 1 && F >= 1 && Hd <= 256 && F <= 256, "h3d_field_pack_x3_device / _x2_device: widths up to 256 (got %d, %d)", Hd, F);
-    H3D_REQUIRE(h3d::aligned16(blob_), "h3d_field_pack_x3_device / _x2_device: the blob must be 16-byte aligned");
+bool widths_ok(int Hd, int F) { return Hd >= 1 && F >= 1 && Hd <= 256 && F <= 256; }
+
+int field_pack(const h3d_field_params* p, int Hd, int F, void* blob, bool x2) {
+    H3D_REQUIRE(p && blob, "h3d_field_pack_x3 / _x2: null pointer");
+    H3D_REQUIRE(widths_ok(Hd, F), "h3d_field_pack_x3 / _x2: widths up to 256 (got %d, %d)", Hd, F);
+    const PackArgs A = make_pack_args(p, Hd, F, blob, x2);
+    memset(A.blob, 0, A.L.total);
+    const auto whole = [](float v) { return v; };
+    for (int j = 0; j < kPackJobs; ++j) pack_job(A.job[j], A.L, A.blob, 0, 1, 0, 1, whole);
+    pack_tail(A, 0, 1, whole);
+    return H3D_OK;
+}
+
+int field_pack_device(const h3d_field_params* p, int Hd, int F, void* blob, bool x2, h3d_stream_t stream) {
+    H3D_REQUIRE(p && blob, "h3d_field_pack_x3_device / _x2_device: null pointer");
+    H3D_REQUIRE(widths_ok(Hd, F), "h3d_field_pack_x3_device / _x2_device: widths up to 256 (got %d, %d)", Hd, F);
+    H3D_REQUIRE(h3d::aligned16(blob), "h3d_field_pack_x3_device / _x2_device: the blob must be 16-byte aligned");
     H3D_REQUIRE(p->w_coord && p->b_coord && p->w_geo && p->b_geo && p->w_sigma && p->b_sigma && p->w_color && p->b_color && p->w_rgb &&
                 p->b_rgb && p->w_feat && p->b_feat, "h3d_field_pack_x3_device / _x2_device: null parameter pointer");
     for (int l = 0; l < 4; ++l) H3D_REQUIRE(p->w_film[l] && p->b_film[l], "h3d_field_pack_x3_device / _x2_device: null FiLM parameter pointer");
-    PackArgs A{};
-    A.L = make_layout(Hd, F, x2);
-    A.p = *p; A.blob = static_cast<unsigned char*>(blob_); A.Hd = Hd; A.F = F; A.x2 = x2 ? 1 : 0;
-    const LayoutX3& L = A.L;
-    int n = 0;
-    auto job = [&](int64_t dst, const float* w, int ld, int in_begin, int in_count, int n_out, int KSm, int kind, int s_rows, int s_begin,
-                   int s_count, int inv_slot, float in_scale) {
-        A.job[n++] = PackJob{w, ld, in_begin, in_count, n_out, KSm, kind, dst, s_rows, ld, s_begin, s_count, inv_slot, in_scale};
-    };
-    const int acc = x2 ? 2 : 1;
-    job(L.w[W_COORD], p->w_coord, 3, 0, 3, Hd, 1, 0, Hd, 0, 3, W_COORD, kSIn);
-    job(L.w[W_GEO], p->w_geo, 31, 0, 31, Hd, 2, 0, Hd, 0, 31, W_GEO, kSIn);
-    job(L.w[W_F0A], p->w_film[0], 2 * Hd, 0, Hd, Hd, L.KS, acc, Hd, 0, 2 * Hd, W_F0A, kSA);      // both halves: one scale (same accumulators)
-    job(L.w[W_F0B], p->w_film[0], 2 * Hd, Hd, Hd, Hd, L.KS, acc, Hd, 0, 2 * Hd, W_F0B, kSA);
-    for (int l = 1; l < 4; ++l) job(L.w[W_F1 + l - 1], p->w_film[l], Hd, 0, Hd, Hd, L.KS, acc, Hd, 0, Hd, W_F1 + l - 1, kSA);
-    job(L.w[W_COLOR], p->w_color, Hd + 3, 3, Hd, Hd, L.KS, acc, Hd, 0, Hd + 3, W_COLOR, kSA);
-    job(L.w[W_COLOR] + (int64_t)L.KS * L.NT * 2 * 64 * 8 * 2, p->w_color, Hd + 3, 0, 3, Hd, 1, 0, Hd, 0, Hd + 3, -1, kSA);
-    job(L.w[W_FEAT], p->w_feat, Hd, 0, Hd, F, L.KS, acc, F, 0, Hd, W_FEAT, kSA);
-    if (n != kPackJobs) return H3D_EINVAL;
+    const PackArgs A = make_pack_args(p, Hd, F, blob, x2);
     hipStream_t st = static_cast<hipStream_t>(stream);
     h3d::pre_launch();
-    if (hipMemsetAsync(A.blob, 0, (size_t)L.total, st) != hipSuccess) return h3d::launch_status("h3d_field_pack_device (memset)");
+    if (hipMemsetAsync(A.blob, 0, (size_t)A.L.total, st) != hipSuccess) return h3d::launch_status("h3d_field_pack_device (memset)");
     hipLaunchKernelGGL(field_pack_kernel, dim3(kPackJobs + 1, kPackSplit), dim3(256), 0, st, A);
     return h3d::launch_status("h3d_field_pack_device");
 }
 
-}  // namespace
-
-extern "C" int h3d_field_pack_x3_device(const h3d_field_params* p, int Hd, int F, void* blob, h3d_stream_t stream) {
-    return field_pack_device(p, Hd, F, blob, false, stream);
-}
-extern "C" int h3d_field_pack_x2_device(const h3d_field_params* p, int Hd, int F, void* blob, h3d_stream_t stream) {
-    return field_pack_device(p, Hd, F, blob, true, stream);
-}
-
-extern "C" int h3d_field_pack_x3(const h3d_field_params* p, int Hd, int F, void* blob) { return field_pack(p, Hd, F, blob, false); }
-extern "C" int h3d_field_pack_x2(const h3d_field_params* p, int Hd, int F, void* blob) { return field_pack(p, Hd, F, blob, true); }
-extern "C" int64_t h3d_field_pack_x2_size(int Hd, int F) {
-    if (Hd < 1 || F < 1 || Hd > 256 || F > 256) return -1;
-    return make_layout(Hd, F, true).total;
-}
-extern "C" int h3d_field_x2_layout(int Hd, int F, int64_t* out, int n_out) {
-    H3D_REQUIRE(out && n_out >= 20, "h3d_field_x2_layout: need room for 20 values");
-    H3D_REQUIRE(Hd >= 1 && F >= 1 && Hd <= 256 && F <= 256, "h3d_field_x2_layout: widths up to 256 (got %d, %d)", Hd, F);
-    const LayoutX3 L = make_layout(Hd, F, true);
+int field_layout(int Hd, int F, int64_t* out, int n_out, bool x2) {
+    const char* name = x2 ? "h3d_field_x2_layout" : "h3d_field_x3_layout";
+    H3D_REQUIRE(out && n_out >= 20, "%s: need room for 20 values", name);
+    H3D_REQUIRE(widths_ok(Hd, F), "%s: widths up to 256 (got %d, %d)", name, Hd, F);
+    const LayoutX3 L = make_layout(Hd, F, x2);
     int i = 0;
     out[i++] = L.NT; out[i++] = L.KS; out[i++] = L.HdP; out[i++] = L.stages;
     for (int w = 0; w < W_COUNT; ++w) out[i++] = L.w[w];
     out[i++] = L.inv_scale; out[i++] = L.bias; out[i++] = L.b_feat; out[i++] = L.head_w; out[i++] = L.head_inv;
     out[i++] = L.head_b; out[i++] = L.total;
     return H3D_OK;
+}
+
+int64_t field_pack_size(int Hd, int F, bool x2) { return widths_ok(Hd, F) ? make_layout(Hd, F, x2).total : -1; }
+
+}  // namespace
+
+extern "C" int h3d_field_x3_layout(int Hd, int F, int64_t* out, int n_out) { return field_layout(Hd, F, out, n_out, false); }
+extern "C" int h3d_field_x2_layout(int Hd, int F, int64_t* out, int n_out) { return field_layout(Hd, F, out, n_out, true); }
+extern "C" int64_t h3d_field_pack_x3_size(int Hd, int F) { return field_pack_size(Hd, F, false); }
+extern "C" int64_t h3d_field_pack_x2_size(int Hd, int F) { return field_pack_size(Hd, F, true); }
+extern "C" int h3d_field_pack_x3(const h3d_field_params* p, int Hd, int F, void* blob) { return field_pack(p, Hd, F, blob, false); }
+extern "C" int h3d_field_pack_x2(const h3d_field_params* p, int Hd, int F, void* blob) { return field_pack(p, Hd, F, blob, true); }
+extern "C" int h3d_field_pack_x3_device(const h3d_field_params* p, int Hd, int F, void* blob, h3d_stream_t stream) {
+    return field_pack_device(p, Hd, F, blob, false, stream);
+}
+extern "C" int h3d_field_pack_x2_device(const h3d_field_params* p, int Hd, int F, void* blob, h3d_stream_t stream) {
+    return field_pack_device(p, Hd, F, blob, true, stream);
 }
 
 static int check_x3(const void* packed, const float* points, const float* geo, const float* freq, const float* phase,

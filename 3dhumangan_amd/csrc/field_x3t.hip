@@ -14,6 +14,7 @@
 // operands so that the sum over a ray's samples is a sum over accumulator registers -- the [N, F+4] field tensor never
 // exists in HBM.  MFMA-bound: 2*(7*Hd^2 + 41*Hd) flop per sample (x3 products issued).
 #include "x3t_common.hpp"
+#include "field_pack.hpp"
 #include <algorithm>
 #include <math.h>
 #include <stdio.h>
@@ -655,13 +656,6 @@ int launch(const Args& A, int B, int64_t groups, hipStream_t st) {
     }
 }
 
-float pow2_scale(const float* w, int64_t n, float target) {
-    float mx = 0.f;
-    for (int64_t i = 0; i < n; ++i) mx = fmaxf(mx, fabsf(w[i]));
-    if (mx == 0.f) return 1.f;
-    return exp2f(floorf(log2f(target / mx)));
-}
-
 bool widths_ok(int Hd, int F) { return Hd >= 1 && F >= 1 && Hd <= 448 && F <= 448; }
 
 int check_x3t(const void* packed, const float* points, const float* geo, const float* freq, const float* phase,
@@ -705,6 +699,48 @@ extern "C" int h3d_field_pack_x3t(const h3d_field_params* p, int Hd, int F, void
 extern "C" int h3d_field_pack_x2t(const h3d_field_params* p, int Hd, int F, void* blob) { return field_pack_t(p, Hd, F, blob, true); }
 
 namespace {
+// ---- weight packing (host).  The arithmetic is field_pack.hpp's; what is written here is where the bytes go: the tile-major
+// layouts of x3t_common.hpp ("Weight layouts of a matrix").
+
+float pow2_scale(const float* w, int64_t n, float target) {
+    float mx = 0.f;
+    for (int64_t i = 0; i < n; ++i) mx = fmaxf(mx, fabsf(w[i]));
+    return pow2_scale_of(mx, target);
+}
+
+// slice m -> A fragments in the x3 format, [k-step][hi | lo][64][8] f16 (scaled), KSm k-steps starting at byte `phase_off` of
+// every tile; tiles are `tile_stride` bytes apart.
+void x3t_pack_f16(const WeightSlice& m, int NT, int64_t tile_stride, int64_t phase_off, int KSm, float scale, unsigned char* dst8, bool acc_order) {
+    for (int nt = 0; nt < NT; ++nt)
+        for (int ks = 0; ks < KSm; ++ks) {
+            uint16_t* dst = reinterpret_cast<uint16_t*>(dst8 + (int64_t)nt * tile_stride + phase_off + (int64_t)ks * 2048);
+            for (int lane = 0; lane < 64; ++lane)
+                for (int e = 0; e < 8; ++e)
+                    split_f16(m.at(32 * nt + (lane & 31), slot_k(acc_order, ks, lane >> 5, e), scale), dst[lane * 8 + e], dst[64 * 8 + lane * 8 + e]);
+        }
+}
+
+// x3t_pack_f16 for the x2 tier, x2c format (see x3t_tile_bytes): accumulator-order matrices only, KSm (even) k-steps starting at
+// byte `phase_off` (a K-tile boundary) of every tile: per K-tile [hi fragment 2T | lo record | hi fragment 2T + 1], 3 KiB.
+void x3t_pack_x2(const WeightSlice& m, int NT, int64_t tile_stride, int64_t phase_off, int KSm, float scale, unsigned char* dst) {
+    for (int nt = 0; nt < NT; ++nt)
+        for (int T = 0; T < KSm / 2; ++T) {
+            unsigned char* kt = dst + (int64_t)nt * tile_stride + phase_off + (int64_t)T * 3072;
+            for (int lane = 0; lane < 64; ++lane) {
+                uint16_t h16[16];
+                unsigned rec[8];
+                x2_lane_tile(m, scale, 32 * nt + (lane & 31), lane >> 5, T, h16, rec);
+                for (int j = 0; j < 2; ++j)
+                    for (int e = 0; e < 8; ++e) reinterpret_cast<uint16_t*>(kt + j * 2048)[lane * 8 + e] = h16[8 * j + e];
+                // lo record: code dwords 3-5 (slots 16-31) and the scale dword; the hi codes (dwords 0-2) are what
+                // v_cvt_scalef32_pk32_fp6_f16 makes of the hi fragments with that scale: not stored
+                unsigned* cd = reinterpret_cast<unsigned*>(kt + 1024);
+                for (int d = 0; d < 3; ++d) cd[lane * 4 + d] = rec[3 + d];
+                cd[lane * 4 + 3] = rec[6] & 0xffu;                   // the scale byte alone (the matrix instruction reads byte 0, the conversion shifts it)
+            }
+        }
+}
+
 int field_pack_t(const h3d_field_params* p, int Hd, int F, void* blob_, bool x2) {
     H3D_REQUIRE(p && blob_, "h3d_field_pack_x3t: null pointer");
     H3D_REQUIRE(widths_ok(Hd, F), "h3d_field_pack_x3t: widths up to 448 (got %d, %d)", Hd, F);
@@ -715,46 +751,46 @@ int field_pack_t(const h3d_field_params* p, int Hd, int F, void* blob_, bool x2)
     const float target = 8192.f;
     auto dst = [&](int wi) { return blob + L.w[wi]; };
     // accumulator-order matrices: x3 format (hi + lo fragments) or, the x2 tier's blob, x2c (hi fragments + lo records, 3 KiB per K-tile)
-    auto pack_acc = [&](const float* w, int ld, int in_begin, int in_count, int n_out, int ks0, int KSm, float sc, int wi) {
+    auto pack_acc = [&](const WeightSlice& m, int ks0, int KSm, float sc, int wi) {
         const int64_t stride = tile_bytes_of(wi, L.KS, x2);
-        if (x2) x3t_pack_x2(w, ld, in_begin, in_count, n_out, L.NT, stride, x3t_kstep_off<true>(ks0), KSm, sc, dst(wi));
-        else x3t_pack_f16(w, ld, in_begin, in_count, n_out, L.NT, stride, x3t_kstep_off<false>(ks0), KSm, sc, dst(wi), true);
+        if (x2) x3t_pack_x2(m, L.NT, stride, x3t_kstep_off<true>(ks0), KSm, sc, dst(wi));
+        else x3t_pack_f16(m, L.NT, stride, x3t_kstep_off<false>(ks0), KSm, sc, dst(wi), true);
     };
     // input layers: natural K order
     {
         const float sc = pow2_scale(p->w_coord, (int64_t)Hd * 3, target);
-        x3t_pack_f16(p->w_coord, 3, 0, 3, Hd, L.NT, tile_bytes_of(W_COORD, L.KS, x2), 0, 1, sc, dst(W_COORD), false);
+        x3t_pack_f16({p->w_coord, 3, 0, 3, Hd}, L.NT, tile_bytes_of(W_COORD, L.KS, x2), 0, 1, sc, dst(W_COORD), false);
         invs[W_COORD] = 1.f / (sc * kSInT);
     }
     {
         const float sc = pow2_scale(p->w_geo, (int64_t)Hd * 31, target);
-        x3t_pack_f16(p->w_geo, 31, 0, 31, Hd, L.NT, tile_bytes_of(W_GEO, L.KS, x2), 0, 2, sc, dst(W_GEO), false);
+        x3t_pack_f16({p->w_geo, 31, 0, 31, Hd}, L.NT, tile_bytes_of(W_GEO, L.KS, x2), 0, 2, sc, dst(W_GEO), false);
         invs[W_GEO] = 1.f / (sc * kSInT);
     }
     // FiLM 0: both K halves accumulate into the same registers -> one scale; k-steps [0, KS) coordinate half, [KS, 2KS) geometry half
     {
         const float sc = pow2_scale(p->w_film[0], (int64_t)Hd * 2 * Hd, target);
-        pack_acc(p->w_film[0], 2 * Hd, 0, Hd, Hd, 0, L.KS, sc, W_F0);
-        pack_acc(p->w_film[0], 2 * Hd, Hd, Hd, Hd, L.KS, L.KS, sc, W_F0);
+        pack_acc({p->w_film[0], 2 * Hd, 0, Hd, Hd}, 0, L.KS, sc, W_F0);
+        pack_acc({p->w_film[0], 2 * Hd, Hd, Hd, Hd}, L.KS, L.KS, sc, W_F0);
         invs[W_F0] = 1.f / sc;
     }
     for (int l = 1; l < 4; ++l) {
         const float sc = pow2_scale(p->w_film[l], (int64_t)Hd * Hd, target);
-        pack_acc(p->w_film[l], Hd, 0, Hd, Hd, 0, L.KS, sc, W_F0 + l);
+        pack_acc({p->w_film[l], Hd, 0, Hd, Hd}, 0, L.KS, sc, W_F0 + l);
         invs[W_F0 + l] = 1.f / sc;
     }
     // colour layer: KS k-steps over the hidden features (columns 3..), one k-step over the view direction (columns
     // 0..2, natural order); one scale for the whole matrix (same accumulators), both inputs unscaled
     {
         const float sc = pow2_scale(p->w_color, (int64_t)Hd * (Hd + 3), target);
-        pack_acc(p->w_color, Hd + 3, 3, Hd, Hd, 0, L.KS, sc, W_COLOR);
-        x3t_pack_f16(p->w_color, Hd + 3, 0, 3, Hd, L.NT, tile_bytes_of(W_COLOR, L.KS, x2),
+        pack_acc({p->w_color, Hd + 3, 3, Hd, Hd}, 0, L.KS, sc, W_COLOR);
+        x3t_pack_f16({p->w_color, Hd + 3, 0, 3, Hd}, L.NT, tile_bytes_of(W_COLOR, L.KS, x2),
                      x2 ? x3t_kstep_off<true>(L.KS) : x3t_kstep_off<false>(L.KS), 1, sc, dst(W_COLOR), false);
         invs[W_COLOR] = 1.f / sc;
     }
     {
         const float sc = pow2_scale(p->w_feat, (int64_t)F * Hd, target);
-        pack_acc(p->w_feat, Hd, 0, Hd, F, 0, L.KS, sc, W_FEAT);
+        pack_acc({p->w_feat, Hd, 0, Hd, F}, 0, L.KS, sc, W_FEAT);
         invs[W_FEAT] = 1.f / sc;
     }
     float* bias = reinterpret_cast<float*>(blob + L.bias);
@@ -766,50 +802,36 @@ int field_pack_t(const h3d_field_params* p, int Hd, int F, void* blob_, bool x2)
     }
     float* bf = reinterpret_cast<float*>(blob + L.b_feat);
     for (int nn = 0; nn < F; ++nn) bf[nn] = p->b_feat[nn];
-    // heads: one 32-row A tile whose rows 0..3 are sigma, r, g, b (own power-of-two scale each), K in accumulator order
-    uint16_t* hw = reinterpret_cast<uint16_t*>(blob + L.head_w);
+    // heads: one 32-row A tile whose rows 0..3 are sigma, r, g, b (own power-of-two scale each), K in accumulator order: row hd
+    // is lanes hd and 32 + hd of every k-step, as hi + lo fragments or (x2) hi fragments + records split over the two lo planes
+    unsigned char* hbase = blob + L.head_w;
     float* hinv = reinterpret_cast<float*>(blob + L.head_inv);
     float* hb = reinterpret_cast<float*>(blob + L.head_b);
     for (int hd = 0; hd < 4; ++hd) {
-        const float* w = hd == 0 ? p->w_sigma : p->w_rgb + (int64_t)(hd - 1) * Hd;
-        const float sc = pow2_scale(w, Hd, target);
+        const WeightSlice row{hd == 0 ? p->w_sigma : p->w_rgb + (int64_t)(hd - 1) * Hd, Hd, 0, Hd, 1};
+        const float sc = pow2_scale(row.w, Hd, target);
         hinv[hd] = 1.f / sc;
         hb[hd] = hd == 0 ? p->b_sigma[0] : p->b_rgb[hd - 1];
-        if (x2) {      // rows 0..3 of the head tile as hi fragments + records (lane = 32 * hh + row)
-            unsigned char* hbase = blob + L.head_w;
-            for (int T = 0; T < L.KS / 2; ++T)
-                for (int hh = 0; hh < 2; ++hh) {
-                    float hi[16], lo[16];
-                    const int lane = 32 * hh + hd;
-                    for (int j = 0; j < 2; ++j)
-                        for (int e = 0; e < 8; ++e) {
-                            const int k = x3t_acc_k(2 * T + j, hh, e);
-                            const float v = k < Hd ? w[k] * sc : 0.f;
-                            const uint16_t h16 = x3t_f32_to_f16_rn(v);
-                            hi[8 * j + e] = x3t_f16_to_f32(h16);
-                            lo[8 * j + e] = v - hi[8 * j + e];
-                            reinterpret_cast<uint16_t*>(hbase + (int64_t)(2 * T + j) * 2048)[lane * 8 + e] = h16;
-                        }
+        auto plane = [&](int ks, int lo) { return hbase + (int64_t)ks * 2048 + lo * 1024; };
+        for (int hh = 0; hh < 2; ++hh) {
+            const int lane = 32 * hh + hd;
+            if (x2) {
+                for (int T = 0; T < L.KS / 2; ++T) {
+                    uint16_t h16[16];
                     unsigned rec[8];
-                    x2_make_record(hi, lo, rec);
-                    for (int j = 0; j < 2; ++j)
-                        for (int d = 0; d < 4; ++d)
-                            reinterpret_cast<unsigned*>(hbase + (int64_t)(2 * T + j) * 2048 + 1024)[lane * 4 + d] = rec[4 * j + d];
+                    x2_lane_tile(row, sc, 0, hh, T, h16, rec);
+                    for (int j = 0; j < 2; ++j) {
+                        for (int e = 0; e < 8; ++e) reinterpret_cast<uint16_t*>(plane(2 * T + j, 0))[lane * 8 + e] = h16[8 * j + e];
+                        for (int d = 0; d < 4; ++d) reinterpret_cast<unsigned*>(plane(2 * T + j, 1))[lane * 4 + d] = rec[4 * j + d];
+                    }
                 }
-            continue;
+            } else {
+                for (int ks = 0; ks < L.KS; ++ks)
+                    for (int e = 0; e < 8; ++e)
+                        split_f16(row.at(0, acc_k(ks, hh, e), sc), reinterpret_cast<uint16_t*>(plane(ks, 0))[lane * 8 + e],
+                                  reinterpret_cast<uint16_t*>(plane(ks, 1))[lane * 8 + e]);
+            }
         }
-        for (int ks = 0; ks < L.KS; ++ks)
-            for (int hh = 0; hh < 2; ++hh)
-                for (int e = 0; e < 8; ++e) {
-                    const int k = x3t_acc_k(ks, hh, e);
-                    const float v = k < Hd ? w[k] * sc : 0.f;
-                    const uint16_t hi = x3t_f32_to_f16_rn(v), lo = x3t_f32_to_f16_rn(v - x3t_f16_to_f32(hi));
-                    const int64_t base = ((int64_t)ks * 2) * 64 * 8 + (32 * hh + hd) * 8 + e;      // lane = 32*hh + row
-                    hw[base] = hi;
-                    hw[base + 64 * 8] = lo;
-                }
-        hinv[hd] = 1.f / sc;
-        hb[hd] = hd == 0 ? p->b_sigma[0] : p->b_rgb[hd - 1];
     }
     return H3D_OK;
 }

@@ -17,16 +17,15 @@
 //                k-steps 2t and 2t+1 ("accumulator order", the same permutation as x3_common.hpp):
 //                    feature(ks, h, e) = 32*(ks/2) + (e & 3) + 8*(2*(ks & 1) + (e >> 2)) + 4*h
 //                so the epilogue of a unit writes its fragments with two lane-local ds_write_b128 per plane, no
-//                transposition; the host packs the K dimension of every matrix fed that way accordingly.  Matrices
-//                fed from memory (coordinates, geometry features, view direction, shared-MLP activations) use the
-//                natural order k = 16*ks + 8*h + e.
+//                transposition; the packers order the K dimension of every matrix fed that way accordingly
+//                (field_pack.hpp: acc_k).  Matrices fed from memory (coordinates, geometry features, view direction,
+//                shared-MLP activations) use the natural order k = 16*ks + 8*h + e.
 //   work split   a *unit* is (feature tile nt, sample tile mt).  Wave w owns the full tiles nt = w, w+4, .. (< 4*NTF)
 //                for both sample tiles and, when the tile count is 4*NTF + 2, one extra unit
 //                (nt = 4*NTF + (w >> 1), mt = w & 1): 2*NTF + NX accumulator tiles per wave, perfectly balanced for the
 //                even tile counts the hosts pad to (12 for width 384, 14 for 420).
 #pragma once
 #include "x3_common.hpp"
-#include <string.h>
 
 namespace h3d {
 
@@ -35,8 +34,6 @@ constexpr int kX3tDepth = 4;         // weight k-steps in flight per wave (regis
 
 // byte offset of fragment plane (mt, ks, plane) inside an activation tile with KS k-steps per sample tile
 __device__ __forceinline__ int x3t_frag(int KS, int mt, int ks, int plane) { return ((mt * KS + ks) * 2 + plane) * 1024; }
-
-__host__ __device__ inline int x3t_acc_k(int ks, int hh, int e) { return 32 * (ks / 2) + (e & 3) + 8 * (2 * (ks & 1) + (e >> 2)) + 4 * hh; }
 
 // Which units a wave owns.
 template <int NTF, int NX>
@@ -88,7 +85,7 @@ struct X3tRing {
     AF a[kX3tDepth];
 };
 
-// Weight layouts of a matrix, per tile (x3t_pack_f16 / x3t_pack_x2):
+// Weight layouts of a matrix, per tile (written by field_x3t.hip: x3t_pack_f16 / x3t_pack_x2 and lib/generators/synthesis_pack.py):
 //   x3 format   [k-step][hi | lo][64 lanes][16 B]: 2 KiB per k-step (tiers P = 1, 2, 3; the short input phases of every tier)
 //   x2c format  (round 6, tier P = 4) per K-tile T (k-steps 2T, 2T + 1) 3 KiB:
 //                   +0     f16 hi fragment of k-step 2T
@@ -451,133 +448,6 @@ __device__ __forceinline__ float x3t_f16_sum(unsigned hw, unsigned lw, int half)
 __device__ __forceinline__ float x3t_bf16_sum(unsigned hw, unsigned lw, int half) {
     const unsigned a = half ? (hw & 0xffff0000u) : (hw << 16), b = half ? (lw & 0xffff0000u) : (lw << 16);
     return __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
-}
-
-// ---- host-side packing (shared by field_x3t.hip; the synthesis side packs with torch, same layout) ------------------
-
-inline uint16_t x3t_f32_to_f16_rn(float f) {            // round-to-nearest-even, handles subnormals; inputs are finite
-    uint32_t x;
-    memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    x &= 0x7fffffffu;
-    if (x >= 0x47800000u) return (uint16_t)(sign | 0x7bffu);
-    if (x < 0x38800000u) {
-        if (x < 0x33000000u) return (uint16_t)sign;
-        const uint32_t mant = (x & 0x7fffffu) | 0x800000u;
-        const int shift = 126 - (int)(x >> 23);
-        uint32_t r = mant >> shift;
-        const uint32_t rem = mant & ((1u << shift) - 1), half = 1u << (shift - 1);
-        if (rem > half || (rem == half && (r & 1))) ++r;
-        return (uint16_t)(sign | r);
-    }
-    uint32_t r = ((x - 0x38000000u) >> 13);
-    const uint32_t rem = x & 0x1fffu;
-    if (rem > 0x1000u || (rem == 0x1000u && (r & 1))) ++r;
-    return (uint16_t)(sign | r);
-}
-
-inline float x3t_f16_to_f32(uint16_t v) {
-    const uint32_t sign = (uint32_t)(v & 0x8000u) << 16;
-    uint32_t e = (v >> 10) & 0x1f, m = v & 0x3ffu, x;
-    if (e == 0) {
-        if (m == 0) x = sign;
-        else {
-            int s = 0;
-            while (!(m & 0x400u)) { m <<= 1; ++s; }
-            x = sign | ((uint32_t)(113 - s) << 23) | ((m & 0x3ffu) << 13);
-        }
-    } else x = sign | ((e + 112) << 23) | (m << 13);
-    float f;
-    memcpy(&f, &x, 4);
-    return f;
-}
-
-// W [n_out, ld] row-major, K range [in_begin, in_begin + in_count) -> A fragments in the x3 format, [k-step][hi | lo][64][8] f16
-// (scaled), KSm k-steps starting at byte `phase_off` of every tile; tiles are `tile_stride` bytes apart.
-inline void x3t_pack_f16(const float* w, int ld, int in_begin, int in_count, int n_out, int NT, int64_t tile_stride, int64_t phase_off, int KSm,
-                         float scale, unsigned char* dst8, bool acc_order) {
-    for (int nt = 0; nt < NT; ++nt)
-        for (int ks = 0; ks < KSm; ++ks)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int k = acc_order ? x3t_acc_k(ks, lane >> 5, e) : 16 * ks + 8 * (lane >> 5) + e;
-                    const int nn = 32 * nt + (lane & 31);
-                    float v = 0.f;
-                    if (k < in_count && nn < n_out) v = w[(int64_t)nn * ld + in_begin + k] * scale;
-                    const uint16_t hi = x3t_f32_to_f16_rn(v);
-                    const uint16_t lo = x3t_f32_to_f16_rn(v - x3t_f16_to_f32(hi));
-                    uint16_t* dst = reinterpret_cast<uint16_t*>(dst8 + (int64_t)nt * tile_stride + phase_off + (int64_t)ks * 2048);
-                    dst[lane * 8 + e] = hi;
-                    dst[64 * 8 + lane * 8 + e] = lo;
-                }
-}
-
-// ---- x2 packing (host): fp6 (e2m3) codes and block scales -----------------------------------------------------------
-inline unsigned x2_e2m3_code(float v) {            // round-to-nearest-even on the code grid, saturating at 7.5
-    const unsigned sign = v < 0.f ? 32u : 0u;
-    const float a = fminf(fabsf(v), 7.5f);
-    const float step = a < 2.f ? 0.125f : a < 4.f ? 0.25f : 0.5f;
-    const float q = nearbyintf(a / step) * step;   // default rounding mode: ties to even; spacing doubles exactly at 2 and 4
-    unsigned c;
-    if (q < 2.f) c = (unsigned)(q * 8.f);
-    else if (q < 4.f) c = 16u + (unsigned)((q - 2.f) * 4.f);
-    else c = 24u + (unsigned)((q - 4.f) * 2.f);
-    return sign | c;
-}
-
-// 32 B record of one lane and K-tile from its 16 (already scaled) weights' f16 hi values and fp32 residuals
-inline void x2_make_record(const float (&hi)[16], const float (&lo)[16], unsigned (&rec)[8]) {
-    float mx = 0.f;
-    for (int i = 0; i < 16; ++i) mx = fmaxf(mx, fabsf(hi[i]));
-    int ea = mx > 0.f ? (int)floorf(log2f(7.5f / mx)) : 0;
-    if (ea > 100) ea = 100;
-    if (ea < -100) ea = -100;
-    for (bool sat = true; sat && ea > -100;) {          // several steps when the hi values are f16 subnormals (|lo| up to |hi| / 2)
-        sat = false;
-        for (int i = 0; i < 16; ++i) sat = sat || fabsf(lo[i]) * kX2Rho * ldexpf(1.f, ea) > 7.5f;
-        if (sat) --ea;
-    }
-    const float alpha = ldexpf(1.f, ea);
-    for (int d = 0; d < 8; ++d) rec[d] = 0;
-    for (int sl = 0; sl < 32; ++sl) {
-        const float v = sl < 16 ? hi[sl] * alpha : lo[sl - 16] * alpha * kX2Rho;
-        const uint64_t code = x2_e2m3_code(v);
-        const int bit = 6 * sl;
-        rec[bit / 32] |= (unsigned)(code << (bit & 31));
-        if ((bit & 31) > 26) rec[bit / 32 + 1] |= (unsigned)(code >> (32 - (bit & 31)));
-    }
-    rec[6] = rec[7] = (unsigned)(127 - ea) * 0x01010101u;
-}
-
-// x3t_pack_f16 for the x2 tier, x2c format (see x3t_tile_bytes): accumulator-order matrices only, KSm (even) k-steps starting at
-// byte `phase_off` (a K-tile boundary) of every tile: per K-tile [hi fragment 2T | lo record | hi fragment 2T + 1], 3 KiB.
-inline void x3t_pack_x2(const float* w, int ld, int in_begin, int in_count, int n_out, int NT, int64_t tile_stride, int64_t phase_off, int KSm,
-                        float scale, unsigned char* dst) {
-    for (int nt = 0; nt < NT; ++nt)
-        for (int T = 0; T < KSm / 2; ++T) {
-            unsigned char* kt = dst + (int64_t)nt * tile_stride + phase_off + (int64_t)T * 3072;
-            for (int lane = 0; lane < 64; ++lane) {
-                const int nn = 32 * nt + (lane & 31), hh = lane >> 5;
-                float hi[16], lo[16];
-                for (int j = 0; j < 2; ++j)
-                    for (int e = 0; e < 8; ++e) {
-                        const int k = x3t_acc_k(2 * T + j, hh, e);
-                        float v = 0.f;
-                        if (k < in_count && nn < n_out) v = w[(int64_t)nn * ld + in_begin + k] * scale;
-                        const uint16_t h16 = x3t_f32_to_f16_rn(v);
-                        hi[8 * j + e] = x3t_f16_to_f32(h16);
-                        lo[8 * j + e] = v - hi[8 * j + e];
-                        reinterpret_cast<uint16_t*>(kt + j * 2048)[lane * 8 + e] = h16;
-                    }
-                unsigned rec[8];
-                x2_make_record(hi, lo, rec);
-                // lo record: code dwords 3-5 (slots 16-31) and the scale dword; the hi codes (dwords 0-2) are what
-                // v_cvt_scalef32_pk32_fp6_f16 makes of the hi fragments with that scale: not stored
-                unsigned* cd = reinterpret_cast<unsigned*>(kt + 1024);
-                for (int d = 0; d < 3; ++d) cd[lane * 4 + d] = rec[3 + d];
-                cd[lane * 4 + 3] = rec[6] & 0xffu;                   // the scale byte alone (the matrix instruction reads byte 0, the conversion shifts it)
-            }
-        }
 }
 
 }  // namespace h3d

@@ -256,7 +256,7 @@ class SynthesisPlan:
     @staticmethod
     def e2m3_codes(v):
         """fp32 tensor -> 6-bit e2m3 codes (int64): round-to-nearest-even on the code grid, saturating at 7.5 (the same
-        arithmetic as csrc/field_x3.hip: e2m3_code and as v_cvt_scalef32_pk32_fp6_f16)."""
+        arithmetic as csrc/field_pack.hpp: e2m3_code and as v_cvt_scalef32_pk32_fp6_f16)."""
         a = v.abs().clamp(max=7.5)
         step = torch.where(a < 2, torch.full_like(a, 0.125), torch.where(a < 4, torch.full_like(a, 0.25), torch.full_like(a, 0.5)))
         q = torch.round(a / step) * step

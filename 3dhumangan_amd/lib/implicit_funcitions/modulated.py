@@ -70,8 +70,8 @@ class COORDCONCATSIREN(nn.Module):
         self.precision = os.environ.get("H3D_FIELD_PRECISION", default)
         # x2 render: refinement of ill-conditioned last samples on the three-product engine (render_geo; round 6)
         self.refine_last_sample = os.environ.get("H3D_FIELD_REFINE", "1") != "0"
-        # weights packed on the device they live on (round 6; H3D_FIELD_PACK=host: the D2H copy + host packer + H2D copy of rounds 1-5)
-        self.device_pack = os.environ.get("H3D_FIELD_PACK", "device") != "host"
+        # weights packed on the device they live on (round 6); False: D2H copy + host packer + H2D copy -- the same bytes
+        self.device_pack = True
         self.refine_eps = float(os.environ.get("H3D_FIELD_REFINE_EPS", "1e-3"))
         self.refine_capacity = int(os.environ.get("H3D_FIELD_REFINE_CAP", "128"))       # listed units per batch item
         self._refine_buf = None

@@ -59,16 +59,39 @@ def matrix(blob, off, NT, kstot, ks0, n_ks, acc_order):
     return W
 
 
-@pytest.mark.parametrize("Hd", [40, 200, 384, 420])
-def test_field_x3t_pack_decodes_to_the_reference_network(Hd):
-    F = Hd
+def network(Hd):
     torch.manual_seed(Hd)
-    net = impl.COORDCONCATSIREN(input_dim=3, latent_dim=Hd, hidden_dim=Hd, geo_feature_dim=31, output_dim=F + 4, feature_dim=F,
+    net = impl.COORDCONCATSIREN(input_dim=3, latent_dim=Hd, hidden_dim=Hd, geo_feature_dim=31, output_dim=Hd + 4, feature_dim=Hd,
                                 num_blocks=4)
     with torch.no_grad():
         for p in net.parameters():
             if p.dim() == 1:
                 p.add_(0.05 * torch.randn_like(p))
+    return net
+
+
+@pytest.mark.parametrize("Hd", [40, 200, 384, 420])
+def test_field_x3t_pack_decodes_to_the_reference_network(Hd):
+    decode_and_compare(network(Hd), Hd)
+
+
+def test_scale_one_ulp_above_a_power_of_two_keeps_its_headroom():
+    """The matrix scale is the largest 2^e with max|w| * 2^e <= 8192, taken exactly from the exponent bits (csrc/field_pack.hpp:
+    floor_log2).  With max|w| one ulp above 1 the quotient 8192 / max|w| lies within float rounding of 2^13 from below, where
+    floor(log2f(q)) says 13: the scale must be 2^12, as the register engines' packer (h3d_field_pack_x3) reports it."""
+    Hd = 40
+    net = network(Hd)
+    with torch.no_grad():
+        w = net.network[1].layer.weight
+        w.mul_(0.5 / float(w.abs().max()))
+        w[0, 0] = torch.nextafter(torch.tensor(1.0), torch.tensor(2.0))
+    inv = decode_and_compare(net, Hd)
+    assert float(inv["f1"]) == 1.0 / 4096
+
+
+def decode_and_compare(net, Hd):
+    """Decodes the blob of `net`, compares the decoded network with the oracle; returns the blob's inv_scale per matrix."""
+    F = Hd
     blob, lay = pack(net, Hd, F)
     NT, KS, HdP = lay[0:3]
     assert NT % 2 == 0 and NT >= 4 and KS == 2 * NT and HdP == 32 * NT and HdP >= Hd
@@ -129,3 +152,4 @@ def test_field_x3t_pack_decodes_to_the_reference_network(Hd):
                          dirs.double(), input_scaler=scaler)[0]
     # f16 hi + lo carries 22 significant bits of every (scaled) weight; activations are exact here
     assert rel_err(got, ref) < 1e-5
+    return inv

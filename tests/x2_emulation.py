@@ -31,7 +31,7 @@ def f16(v):
 
 
 def acc_k(ks, hh, e):
-    """feature index of k-slot (lane half hh, element e) of k-step ks in accumulator-register order (csrc/field_x3.hip)."""
+    """feature index of k-slot (lane half hh, element e) of k-step ks in accumulator-register order (csrc/field_pack.hpp: acc_k)."""
     return 32 * (ks // 2) + (e & 3) + 8 * (2 * (ks & 1) + (e >> 2)) + 4 * hh
 
 
