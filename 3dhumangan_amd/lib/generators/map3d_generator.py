@@ -9,6 +9,7 @@ differentiable path of lib/generators/differentiable.py runs instead, see Map3DG
     SMPL geometry features              h3d_geo_features                                  (A4)
     FiLM-SIREN + volume integration     h3d_render_fused  (or h3d_neural_field + h3d_ray_integrate)   (A5, A6)
     resize + synthesis input + 9 SPADE blocks + ToRGB      h3d_synthesis                  (A7, A8, A9)
+    (spatial_normalization="none": 9 modulated-conv blocks + ToRGB      h3d_synthesis_mod)
 
 The reference forward is stochastic.  The draws happen here at the same places with torch's device
 RNG; ``jitter=`` / ``noise=`` kwargs inject explicit tensors instead (used by the parity tests).
@@ -25,6 +26,7 @@ from ..components import smpl
 from ..components.ops.bias_act import bias_act
 from . import volume_rendering as vr
 from .differentiable import field_forward, synthesis_forward
+from .modsynth_pack import ModSynthesisPlan
 from .synthesis_pack import SynthesisPlan
 
 
@@ -225,20 +227,56 @@ class _ToRGB(nn.Module):
             self.linear.weight *= 0.25
 
 
+class _ModLayer(nn.Module):
+    """SpatialStyleModLayer parameters (reference map3d_layers.py:50-55): weight [1,1,Cin,Cout], bias [1,1,Cout], affine."""
+
+    def __init__(self, cin, cout, style_dim):
+        super().__init__()
+        self.weight = nn.Parameter(torch.randn(1, 1, cin, cout) * math.sqrt(2 / (1 + 0.2 ** 2)) / math.sqrt(cin))
+        self.bias = nn.Parameter(torch.zeros(1, 1, cout))
+        self.affine = nn.Linear(style_dim, cin)
+        nn.init.kaiming_normal_(self.affine.weight, mode="fan_in", nonlinearity="linear")
+
+
+class _ModBlock(nn.Module):
+    """SynthesisBlock parameters (reference map3d_layers.py:92-95)."""
+
+    def __init__(self, cin, cout, style_dim):
+        super().__init__()
+        self.mod1 = _ModLayer(cin, cout, style_dim)
+        self.mod2 = _ModLayer(cout, cout, style_dim)
+
+
+class _ToRGBLinear(nn.Module):
+    """ToRGB(use_conv=False) (reference map3d_layers.py:340-344)."""
+
+    def __init__(self, c):
+        super().__init__()
+        self.linear = nn.Linear(c, 3)
+        with torch.no_grad():
+            self.linear.weight *= 0.25
+
+
 class SynthesisNetwork(nn.Module):
-    """Parameters of reference map3d_generator.py:14-55; evaluation goes through SynthesisPlan / h3d_synthesis."""
+    """Parameters of reference map3d_generator.py:14-55; evaluation goes through SynthesisPlan / h3d_synthesis
+    (spatial_normalization="batch_norm": SPADE blocks) or ModSynthesisPlan / h3d_synthesis_mod ("none": modulated blocks)."""
 
     def __init__(self, input_dim, style_dim, hidden_dim=256, num_blocks=8, mod_blocks=list(range(8)), name_prefix="m3d",
                  spatial_normalization="instance_norm", map3d_mode="isolated", **_):
         super().__init__()
-        if spatial_normalization != "batch_norm":
-            raise NotImplementedError("only spatial_normalization='batch_norm' (all shipped configs) has a HIP kernel")
+        if spatial_normalization not in ("batch_norm", "none"):
+            raise NotImplementedError("only spatial_normalization='batch_norm' (all shipped configs) and 'none' have a HIP kernel")
+        self.normalization = spatial_normalization
         self.style_dim, self.num_blocks, self.mod_blocks, self.map3d_mode = style_dim, num_blocks, list(mod_blocks), map3d_mode
         net, rgbs = {}, {}
         cin = input_dim
         for i in range(num_blocks):
-            net[f"{name_prefix}_{i}"] = _SpadeBlock(cin, hidden_dim, style_dim)
-            rgbs[f"{name_prefix}_{i}"] = _ToRGB(hidden_dim)
+            if spatial_normalization == "none":
+                net[f"{name_prefix}_{i}"] = _ModBlock(cin, hidden_dim, style_dim)
+                rgbs[f"{name_prefix}_{i}"] = _ToRGBLinear(hidden_dim)
+            else:
+                net[f"{name_prefix}_{i}"] = _SpadeBlock(cin, hidden_dim, style_dim)
+                rgbs[f"{name_prefix}_{i}"] = _ToRGB(hidden_dim)
             cin = hidden_dim
         self.network = nn.ModuleDict(net)
         self.to_rgbs = nn.ModuleDict(rgbs)
@@ -359,8 +397,8 @@ class Map3DGenerator(nn.Module):
                                      if n.startswith(("synthesis_network", "synthesis_input")))
         if self._plan is None or self._plan_key != key:
             sn = self.synthesis_network
-            self._plan = SynthesisPlan(sd, "synthesis_network", "synthesis_input", sn.num_blocks, sn.mod_blocks,
-                                       sn.map3d_mode, device)
+            plan_cls = ModSynthesisPlan if sn.normalization == "none" else SynthesisPlan
+            self._plan = plan_cls(sd, "synthesis_network", "synthesis_input", sn.num_blocks, sn.mod_blocks, sn.map3d_mode, device)
             self._plan_key = key
         return self._plan
 
@@ -533,6 +571,8 @@ class Map3DGenerator(nn.Module):
 
     def _synthesize(self, feature_maps, styles, render_hw, differentiable=False):
         if differentiable:
+            if self.synthesis_network.normalization == "none":
+                raise NotImplementedError("spatial_normalization='none' has no differentiable synthesis path")
             with stage(self, "synthesis"):
                 return synthesis_forward(self, feature_maps, styles, render_hw, (self.gen_height, self.gen_width),
                                          training=self.training, group=getattr(self, "process_group", None))
@@ -564,6 +604,9 @@ class Map3DGenerator(nn.Module):
     def _forward(self, latent, conditions, render_height, render_width, latent_indices=None, differentiable=False, **kwargs):
         if kwargs.get("disable_render", False):
             raise NotImplementedError("disable_render=True is not set by any config and has no HIP path")
+        if differentiable and self.synthesis_network.normalization == "none":
+            raise NotImplementedError("spatial_normalization='none' has the fused inference engine only: the training / "
+                                      "differentiable path is not implemented (call .eval() and leave differentiable unset)")
         num_steps = kwargs.get("num_steps", 24)
         if latent_indices is not None:
             latent = self.latent_pool(latent_indices)

@@ -606,6 +606,45 @@ int h3d_modconv2d(const float* x, const float* smod, const float* dmod, const fl
                   float* out, int B, int Cin, int Cout, int H, int W, int k, h3d_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * P3c  synthesis network without spatial normalisation (spatial_normalization="none"), eval mode, ONE launch
+ *     == SynthesisNetwork.forward (lib/generators/map3d_generator.py:58-97) over SynthesisBlock
+ *     (lib/components/map3d_layers.py:101-112: two SpatialStyleModLayer + LeakyReLU(0.2), skip added after the second
+ *     activation), ToRGB on nn.Linear, fed by SynthesisInput and the bilinear F.interpolate of the feature maps.
+ *
+ * Weight blob: fp32, offsets in FLOATS; W and W*W of a layer packed by h3d_pack_matrix from W^T [Cout, Cin] with
+ *   KB = HdP/8, NT = HdP/32 (HdP = C rounded up to 32); vectors HdP long, zero padded; w_in / b_in / w_rgb as h3d_synthesis.
+ * Per layer:  pixel_style = 1  m = bilinear(M[b, :, map_offset : map_offset + HdP]) (align_corners = False), M the
+ *                              modulation map at render resolution, A G + (b_A + 1 [+ A fixed]) -- the affine commutes
+ *                              with the resize;  y = lrelu((x*m) W * rsqrt((m*m) W2 + eps) + bias)
+ *             pixel_style = 0  y = lrelu((x * md[b, vec_index, 0]) W * md[b, vec_index, 1] + bias): per-image
+ *                              modulation and demodulation vectors, computed by the caller.
+ *             `skip`: the block's input is added to the second layer's y.  to_rgb: rgb += y Wrgb^T + brgb.
+ * M [B, Hr*Wr, m_channels] channels last, 16-byte aligned, padded channels zero; md [B, n_vec, 2, HdP];
+ * rgb [B, 3, H, W] (written).  desc is a HOST pointer (copied into the launch).  Needs input width == hidden width == C.
+ * Returns H3D_EUNSUPPORTED for C > 512 (the [HdP][68] operand tile + 5 KB of tables must fit the 160 KB LDS, four
+ * column tiles per wave); h3d_synthesis_mod_lds_bytes(C) is that plan's size, -1 when unsupported.
+ */
+typedef struct {
+    int32_t pixel_style, map_offset, vec_index, reserved;
+    int64_t w, w2, bias;
+} h3d_modlayer_desc;
+typedef struct {
+    h3d_modlayer_desc layer[2];
+    int32_t skip, to_rgb;
+    int64_t w_rgb;
+} h3d_modblock_desc;
+typedef struct {
+    int32_t n_blocks, C;
+    float eps;
+    int32_t reserved;
+    int64_t w_in, b_in;
+    h3d_modblock_desc block[H3D_MAX_BLOCKS];
+} h3d_modsynth_desc;
+int64_t h3d_synthesis_mod_lds_bytes(int C);
+int h3d_synthesis_mod(const void* blob, const h3d_modsynth_desc* desc, const float* M, int m_channels, int Hr, int Wr,
+                      const float* md, int n_vec, float* rgb, int B, int H, int W, h3d_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Training side: streaming kernels the differentiable generator path is assembled from; the GEMMs between
  * them are library GEMMs (hipBLASLt through torch).  Caller owns every buffer.
  *
