@@ -100,6 +100,8 @@ _SIGNATURES = {
     "h3d_modconv2d": (C.c_int, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "h3d_synthesis_mod_lds_bytes": (C.c_int64, [_i]),
     "h3d_synthesis_mod": (C.c_int, [_p, _p, _p, _i, _i, _i, _p, _i, _p, _i, _i, _i, _p]),
+    "h3d_style_input_lds_bytes": (C.c_int64, [_i, _i]),
+    "h3d_style_input": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "h3d_synthesis_x3_geometry_ok": (C.c_int, [_i, _i, _i, _i]),
     "h3d_synthesis_x3_lds_bytes": (C.c_int64, [_i, _i, _i, _i, _i]),
     "h3d_sample_pdf": (C.c_int, [_p, _p, _p, _p, _l, _i, _i, _f, _p]),

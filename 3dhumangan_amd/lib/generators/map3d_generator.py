@@ -10,6 +10,7 @@ differentiable path of lib/generators/differentiable.py runs instead, see Map3DG
     FiLM-SIREN + volume integration     h3d_render_fused  (or h3d_neural_field + h3d_ray_integrate)   (A5, A6)
     resize + synthesis input + 9 SPADE blocks + ToRGB      h3d_synthesis                  (A7, A8, A9)
     (spatial_normalization="none": 9 modulated-conv blocks + ToRGB      h3d_synthesis_mod)
+    (disable_render=True: the rasterised body condition -> style feature map, no field / rays      h3d_style_input)
 
 The reference forward is stochastic.  The draws happen here at the same places with torch's device
 RNG; ``jitter=`` / ``noise=`` kwargs inject explicit tensors instead (used by the parity tests).
@@ -27,6 +28,7 @@ from ..components.ops.bias_act import bias_act
 from . import volume_rendering as vr
 from .differentiable import field_forward, synthesis_forward
 from .modsynth_pack import ModSynthesisPlan
+from .style_input_pack import StyleInputPlan
 from .synthesis_pack import SynthesisPlan
 
 
@@ -293,8 +295,8 @@ class _CoordInput(nn.Module):
 
 
 class _StyleInput(nn.Module):
-    """SynthesisStyleInput parameters (reference map3d_layers.py:278-343); only reachable through
-    disable_render=True, which no config sets -- kept so reference checkpoints load with strict=True."""
+    """SynthesisStyleInput parameters (reference map3d_layers.py:278-300, built with num_layers=3: two convolutions);
+    evaluated through StyleInputPlan / h3d_style_input when a forward passes disable_render=True."""
 
     def __init__(self, input_dim, latent_dim, output_dim):
         super().__init__()
@@ -349,6 +351,8 @@ class Map3DGenerator(nn.Module):
         self._avg_latent_key = None
         self._plan = None
         self._plan_key = None
+        self._style_plan = None
+        self._style_plan_key = None
         self.stage_timer = None          # set to _stages.StageTimer() to collect per-stage HIP-event timings
 
     # ------------------------------------------------------------------ reference surface
@@ -401,6 +405,18 @@ class Map3DGenerator(nn.Module):
             self._plan = plan_cls(sd, "synthesis_network", "synthesis_input", sn.num_blocks, sn.mod_blocks, sn.map3d_mode, device)
             self._plan_key = key
         return self._plan
+
+    def style_input_plan(self, device):
+        """Packed `synthesis_style_input` weights for `device` (the disable_render=True path), cached per weight version."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        sd = {"synthesis_style_input." + n: v for n, v in self.synthesis_style_input.state_dict().items()}
+        key = (str(device),) + tuple((v.data_ptr(), v._version) for v in sd.values())
+        if self._style_plan is None or self._style_plan_key != key:
+            self._style_plan = StyleInputPlan(sd, "synthesis_style_input", device)
+            self._style_plan_key = key
+        return self._style_plan
 
     # ------------------------------------------------------------------ stages
     def _mapping(self, latent, kwargs):
@@ -580,6 +596,28 @@ class Map3DGenerator(nn.Module):
         return plan.run(feature_maps, styles.reshape(styles.shape[0], -1), render_hw, (self.gen_height, self.gen_width),
                         owner=self)
 
+    @staticmethod
+    def _norender_checks(kwargs, differentiable):
+        """What the disable_render=True path does not cover, refused before anything runs."""
+        if differentiable:
+            raise NotImplementedError("disable_render=True has the fused inference kernel only: the training / differentiable "
+                                      "path is not implemented (call .eval() and leave differentiable unset)")
+        mode = kwargs.get("feature_map_interpolation", "bilinear")
+        if mode != "bilinear":
+            raise NotImplementedError(f"disable_render=True: feature_map_interpolation={mode!r} has no HIP path (the synthesis "
+                                      "engines resize bilinearly)")
+
+    def _style_features(self, latent, conditions, kwargs):
+        """reference :224-236 / :303-318: the style feature map straight from the rasterised body condition.
+        -> feature_maps [B, Hc*Wc, F] (channels last, as render() returns them), (Hc, Wc)"""
+        modal = kwargs["condition_modal_gen"]
+        condition = conditions[modal]
+        if "segments" in modal:
+            condition = condition.unsqueeze(1).to(latent.dtype) / (kwargs["label_dim"] - 1) * 2 - 1
+        plan = self.style_input_plan(latent.device)
+        fmap = plan.run(condition, latent, latent_input=kwargs.get("spade_latent_input", True), owner=self)
+        return fmap, tuple(condition.shape[2:])
+
     def wants_autograd(self, kwargs):
         """Which evaluation a forward call gets.  ``.train()`` mode -> the differentiable path with the reference's train-mode
         semantics (batch-statistics BatchNorm, spectral-norm power iteration), whether or not autograd is recording;
@@ -603,7 +641,16 @@ class Map3DGenerator(nn.Module):
 
     def _forward(self, latent, conditions, render_height, render_width, latent_indices=None, differentiable=False, **kwargs):
         if kwargs.get("disable_render", False):
-            raise NotImplementedError("disable_render=True is not set by any config and has no HIP path")
+            self._norender_checks(kwargs, differentiable)
+            if latent_indices is not None:
+                latent = self.latent_pool(latent_indices)
+            rgb_render = torch.zeros([latent.shape[0], 3, render_height, render_width], dtype=latent.dtype, device=latent.device)
+            if kwargs.get("disable_synthesis", False):
+                return {"rgbs": rgb_render, "rgbs_render": rgb_render}
+            with stage(self, "mapping"):
+                _, styles = self.synthesis_mapping_network(latent)
+            fmap, cond_hw = self._style_features(latent, conditions, kwargs)
+            return {"rgbs": self._synthesize(fmap, styles, cond_hw), "rgbs_render": rgb_render}
         if differentiable and self.synthesis_network.normalization == "none":
             raise NotImplementedError("spatial_normalization='none' has the fused inference engine only: the training / "
                                       "differentiable path is not implemented (call .eval() and leave differentiable unset)")
@@ -630,8 +677,9 @@ class Map3DGenerator(nn.Module):
             return self._staged_forward(latent, conditions, render_height, render_width, truncation_psi, **kwargs)
 
     def _staged_forward(self, latent, conditions, render_height, render_width, truncation_psi, **kwargs):
-        if kwargs.get("disable_render", False):
-            raise NotImplementedError("disable_render=True is not set by any config and has no HIP path")
+        no_render = kwargs.get("disable_render", False)
+        if no_render:
+            self._norender_checks(kwargs, False)
         num_steps = kwargs.get("num_steps", 24)
         B = latent.shape[0]
         fr, ph, styles = self._mapping(latent, kwargs)
@@ -648,14 +696,22 @@ class Map3DGenerator(nn.Module):
             styles = ast + truncation_psi * (styles - ast)
         rk = {k: v for k, v in kwargs.items() if k not in ("coarse_steps", "fine_steps", "render_width", "render_height",
                                                            "staged", "avg_latent", "cache_avg_latent")}
-        rgb_render, fmap, depths, _, _ = self.render(fr, ph, conditions, render_width, render_height,
-                                                     coarse_steps=num_steps, fine_steps=num_steps, staged=True, **rk)
+        feature_hw = (render_height, render_width)
+        if no_render:
+            # reference :303-316: the (truncated) latent feeds the style input; the render image and the depths are zeros
+            rgb_render = torch.zeros([B, 3, render_height, render_width], dtype=latent.dtype, device=latent.device)
+            depths = torch.zeros([B, render_height * render_width, 1], dtype=latent.dtype, device=latent.device)
+            if not kwargs.get("disable_synthesis", False):
+                fmap, feature_hw = self._style_features(latent, conditions, kwargs)
+        else:
+            rgb_render, fmap, depths, _, _ = self.render(fr, ph, conditions, render_width, render_height,
+                                                         coarse_steps=num_steps, fine_steps=num_steps, staged=True, **rk)
         if kwargs.get("disable_synthesis", False):
             from ..components.resample import bilinear_resize
             out = {"rgbs": bilinear_resize(rgb_render.contiguous(), (self.gen_height, self.gen_width)),
                    "rgbs_render": rgb_render}
         else:
-            out = {"rgbs": self._synthesize(fmap, styles, (render_height, render_width)), "rgbs_render": rgb_render}
+            out = {"rgbs": self._synthesize(fmap, styles, feature_hw), "rgbs_render": rgb_render}
         zc = conditions["intrinsics"][:, 0, 0] / conditions["scales"].float()
         depth = ((depths - zc.view(B, 1, 1)) / (kwargs["depth_length"] / 2.0)).clamp(-1.0, 1.0)
         depth_map = depth.reshape(B, render_height, render_width).unsqueeze(1).contiguous()

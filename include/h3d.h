@@ -645,6 +645,27 @@ int h3d_synthesis_mod(const void* blob, const h3d_modsynth_desc* desc, const flo
                       const float* md, int n_vec, float* rgb, int B, int H, int W, h3d_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * P3d  style input of the generator without the 3D render (disable_render=True), ONE launch
+ *     == SynthesisStyleInput.forward (lib/components/map3d_layers.py:315-327) with the latent half of network.0 folded
+ *     into a per-image bias by the caller.  Per pixel p of image b, c = cond[b, :, p]:
+ *         f = sin(Wc c + bc)                       Cc -> L
+ *         h = lrelu_0.2(W0[:, :L] f + bias0[b])    L -> F     bias0[b] = b0 + W0[:, L:2L] normalize_2nd_moment(latent[b])
+ *         h = lrelu_0.2(W1 h + b1)                 F -> F     n_layers == 2 only
+ * cond [B, Cc, Hc, Wc] fp32, Cc = 1 (segments, already mapped to [-1, 1]) or 3 (semantics); bias0 [B, F];
+ * w_coord [Cc + 1][LP]: the rows of Wc^T, then bc, zero padded to LP = L rounded up to 32;
+ * w0_packed = pack(W0[:, :L] [F, L]) with KB = LP/8, NT = FP/32, w1_packed = pack(W1 [F, F]) with KB = FP/8, NT = FP/32
+ * (h3d_pack_matrix, 16-byte aligned; FP = F rounded up to 32); b1 [FP] zero padded; w1_packed / b1 may be NULL with
+ * n_layers == 1.  out [B, Hc*Wc, F] channels last: the low-resolution map h3d_synthesis* / h3d_synthesis_mod read.
+ * Deterministic (no atomics).  H3D_EINVAL: null pointer, Cc outside {1, 3}, a size < 1, n_layers outside {1, 2};
+ * H3D_EUNSUPPORTED: L or F > 512 (the [max(LP, FP)][68] operand tile must fit the 160 KB LDS, four column tiles per
+ * wave); h3d_style_input_lds_bytes(L, F) is that plan's size, -1 when unsupported.
+ */
+int64_t h3d_style_input_lds_bytes(int L, int F);
+int h3d_style_input(const float* cond, const float* bias0, const float* w_coord, const float* w0_packed,
+                    const float* w1_packed, const float* b1, float* out, int B, int Cc, int Hc, int Wc, int L, int F,
+                    int n_layers, h3d_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Training side: streaming kernels the differentiable generator path is assembled from; the GEMMs between
  * them are library GEMMs (hipBLASLt through torch).  Caller owns every buffer.
  *
