@@ -85,8 +85,8 @@ _SIGNATURES = {
                                             _i, _i, _i, _p]),
     "h3d_pack_matrix": (C.c_int, [_p, _i, _i, _i, _i, _i, _i, _p]),
     "h3d_synthesis": (C.c_int, [_p, _p, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _p]),
-    "h3d_synthesis_x3": (C.c_int, [_p, _l, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _p, _i, _i, _p]),
-    "h3d_synthesis_x2": (C.c_int, [_p, _l, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _p, _i, _i, _p]),
+    "h3d_synthesis_x3": (C.c_int, [_p, _l, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _p]),
+    "h3d_synthesis_x2": (C.c_int, [_p, _l, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _p]),
     "h3d_synthesis_x2_extra_lds": (C.c_int, [_i]),
     "h3d_synthesis_x2_guarded": (C.c_int, [_p, _l, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _p, _p]),
     "h3d_synthesis_x3_if": (C.c_int, [_p, _l, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _p, _p]),

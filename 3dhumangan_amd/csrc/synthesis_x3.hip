@@ -46,9 +46,9 @@ struct Args {
     const float* ab;
     float* rgb;
     int table_floats, total_stages, g_channels, Hr, Wr, n_cst, n_ab, H, W, HdP, C, first_skip, n_pixel_blocks;
-    float* state;          // [wave tiles][NT*4 + 1][64 lanes] float4: activations (+ rgb partial sums) between segments
-    int load_state, store_state;
-    int n_tiles;           // 128-pixel tiles per sample (a workgroup walks tiles blockIdx.x, + gridDim.x, ..)
+    // alignas: with n_tiles packed directly behind n_pixel_blocks the compiler allocates and schedules the whole kernel differently
+    // (other VGPR counts; in the shipped x2 variant a ring-stage barrier lost the LDS wait in front of it: tests/test_abi.py)
+    alignas(8) int n_tiles;   // 128-pixel tiles per sample (a workgroup walks tiles blockIdx.x, + gridDim.x, ..)
     int n_walk, tile_first, tile_step;   // the tiles a launch covers: tile_first + i * tile_step, i < n_walk (all of them: 0, 1, n_tiles)
     int heads;             // x2 plans with ToRGB head tables: no zero table of "no ToRGB" weights in LDS (the producers carry no ToRGB)
     int mid_x3;            // x2 plans: the constant-style blocks in front of the first skip block travel / run in the x3 format (MIDX3)
@@ -281,12 +281,12 @@ __device__ __forceinline__ void conv_progressive(f32x16 (&dst)[NT], V8 (&xh)[2 *
 // contribution in the per-contraction attribution, profiles/r5_x2_error_attribution_item14.txt) run on three bf16 products: their
 // stages travel in the x3 format and their fragments are bf16 hi / lo.  Same registers (the 64 of the fp6 records hold the lo
 // fragments), same ring (single-stage acquires, as the x3 tail of gemm_x2_roll).
-template <int NT, int DEPTH, bool SEG, bool X2, bool HEADS = false, bool MIDX3 = false>
+template <int NT, int DEPTH, bool X2, bool HEADS = false, bool MIDX3 = false>
 __global__ __launch_bounds__(256, 1) void synthesis_x3_kernel(Args A) {
     constexpr int KS = 2 * NT, kHdP = NT * 32;       // the host sets A.HdP = 32 NT: table strides are compile-time
     constexpr bool kHeads = HEADS;                   // ToRGB of the skip blocks as a ninth tile of their second convolution (conv_progressive)
-    static_assert(!HEADS || (X2 && !SEG), "ToRGB heads: single-launch x2 plans only");
-    static_assert(!MIDX3 || (X2 && !SEG), "three-product middle blocks: single-launch x2 plans only");
+    static_assert(!HEADS || X2, "ToRGB heads: x2 plans only");
+    static_assert(!MIDX3 || X2, "three-product middle blocks: x2 plans only");
     typedef typename std::conditional<X2, F16, BF16>::type T;
     typedef typename T::vec8 frag8;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -399,20 +399,7 @@ __global__ __launch_bounds__(256, 1) void synthesis_x3_kernel(Args A) {
     f32x16 hacc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // kHeads: rows r = head r & 3, all skip blocks
     (void)hacc;
 
-    const int64_t wtile = (int64_t)b * n_tiles * 4 + (int64_t)tile * 4 + wave;
-    float4* st_io = reinterpret_cast<float4*>(A.state) + wtile * (NT * 4 + 1) * 64 + lane;
-    if (SEG && A.load_state) {
-        // ---- resume: activations (lane-linear, as the previous segment left them) and the ToRGB partial sums
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-                const float4 v = st_io[(nt * 4 + rg) * 64];
-                x[nt][rg * 4 + 0] = v.x; x[nt][rg * 4 + 1] = v.y; x[nt][rg * 4 + 2] = v.z; x[nt][rg * 4 + 3] = v.w;
-            }
-        const float4 r = st_io[NT * 4 * 64];
-        rgb_acc[0] = r.x; rgb_acc[1] = r.y; rgb_acc[2] = r.z;
-    } else {
+    {
         // ---- A8: x0 = sin(w0*i + w1*j + b) in accumulator layout
         const lds_ptr win = lane_base(tab0 + dget(H3D_MAX_BLOCKS, 1), 16 * h);
         const lds_ptr bin = lane_base(tab0 + dget(H3D_MAX_BLOCKS, 2), 16 * h);
@@ -659,15 +646,6 @@ __global__ __launch_bounds__(256, 1) void synthesis_x3_kernel(Args A) {
         // lane halves, so only one of them contributes
         if (h == 0) { rgb_acc[0] += hacc[0]; rgb_acc[1] += hacc[1]; rgb_acc[2] += hacc[2]; }
     }
-    if (SEG && A.store_state) {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg)
-                st_io[(nt * 4 + rg) * 64] = make_float4(x[nt][rg * 4 + 0], x[nt][rg * 4 + 1], x[nt][rg * 4 + 2], x[nt][rg * 4 + 3]);
-        st_io[NT * 4 * 64] = make_float4(rgb_acc[0], rgb_acc[1], rgb_acc[2], 0.f);
-        continue;
-    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float v = rgb_acc[c] + __shfl_xor(rgb_acc[c], 32, 64);
@@ -689,16 +667,16 @@ size_t lds_bytes(const Args& A, int NT, int depth) {
            (size_t)depth * NT * 2048;
 }
 
-template <int NT, int DEPTH, bool SEG, bool X2, bool HEADS = false, bool MIDX3 = false>
-int launch_seg(Args A, int B, int64_t groups, hipStream_t st) {
-    H3D_ALLOW_MAX_LDS((synthesis_x3_kernel<NT, DEPTH, SEG, X2, HEADS, MIDX3>));
+template <int NT, int DEPTH, bool X2, bool HEADS = false, bool MIDX3 = false>
+int launch_variant(Args A, int B, int64_t groups, hipStream_t st) {
+    H3D_ALLOW_MAX_LDS((synthesis_x3_kernel<NT, DEPTH, X2, HEADS, MIDX3>));
     A.n_tiles = (int)groups;
     if (A.tile_step <= 0) { A.tile_first = 0; A.tile_step = 1; }
     A.n_walk = A.tile_first < A.n_tiles ? (A.n_tiles - A.tile_first + A.tile_step - 1) / A.tile_step : 0;
     if (A.n_walk == 0) return H3D_OK;
     groups = A.n_walk;
     // persistent workgroups (one per CU at a time: registers and LDS): about four per CU in total, so that the tables are staged
-    // once per ~n_tiles * B / (4 CUs) tiles while the tail of the launch stays short; segmented runs keep one tile per workgroup
+    // once per ~n_tiles * B / (4 CUs) tiles while the tail of the launch stays short
     static int cus = 0;
     if (!cus) {
         int dev = 0;
@@ -707,25 +685,23 @@ int launch_seg(Args A, int B, int64_t groups, hipStream_t st) {
     }
     static const int per_cu = getenv("H3D_SYNTH_WG_PER_CU") ? atoi(getenv("H3D_SYNTH_WG_PER_CU")) : 4;      // 0: one tile per workgroup
     // (a fallback launch -- run_if -- usually redoes ONE sample of the batch: that sample's workgroups must fill the chip by themselves)
-    const int64_t per_sample = (SEG || per_cu <= 0) ? groups
+    const int64_t per_sample = per_cu <= 0 ? groups
                              : A.run_if ? std::min<int64_t>(groups, cus)
                              : std::max<int64_t>(1, std::min<int64_t>(groups, ((int64_t)per_cu * cus + B - 1) / B));
     h3d::pre_launch();
-    hipLaunchKernelGGL((synthesis_x3_kernel<NT, DEPTH, SEG, X2, HEADS, MIDX3>), dim3((unsigned)per_sample, (unsigned)B), dim3(256),
+    hipLaunchKernelGGL((synthesis_x3_kernel<NT, DEPTH, X2, HEADS, MIDX3>), dim3((unsigned)per_sample, (unsigned)B), dim3(256),
                        lds_bytes(A, NT, DEPTH + (X2 ? 1 : 0)), st, A);
     return h3d::launch_status(X2 ? "h3d_synthesis_x2" : "h3d_synthesis_x3");
 }
 
 template <int NT, int DEPTH, bool X2>
 int launch_one(const Args& A, int B, int64_t groups, hipStream_t st, bool heads = false) {
-    // the state load/store paths are compiled only into the segmented variant (they cost registers)
-    if (A.load_state || A.store_state) return launch_seg<NT, DEPTH, true, X2>(A, B, groups, st);
     if constexpr (X2) {
-        if (A.mid_x3) return heads ? launch_seg<NT, DEPTH, false, true, true, true>(A, B, groups, st)
-                                   : launch_seg<NT, DEPTH, false, true, false, true>(A, B, groups, st);
-        if (heads) return launch_seg<NT, DEPTH, false, true, true>(A, B, groups, st);
+        if (A.mid_x3) return heads ? launch_variant<NT, DEPTH, true, true, true>(A, B, groups, st)
+                                   : launch_variant<NT, DEPTH, true, false, true>(A, B, groups, st);
+        if (heads) return launch_variant<NT, DEPTH, true, true>(A, B, groups, st);
     }
-    return launch_seg<NT, DEPTH, false, X2>(A, B, groups, st);
+    return launch_variant<NT, DEPTH, X2>(A, B, groups, st);
 }
 
 }  // namespace
@@ -738,8 +714,7 @@ extern "C" int h3d_synthesis_x3_geometry_ok(int H, int W, int Hr, int Wr) {
 static int synthesis_x(bool x2, const void* stream, int64_t total_stages, const float* tables, int table_floats,
                        const h3d_synth_desc* desc, const float* G, int g_channels, int Hr, int Wr,
                        const float* cst, int n_cst, const float* ab, int n_ab, float* rgb, int B, int H, int W,
-                       float* state, int load_state, int store_state, h3d_stream_t stream_, int* ovf = nullptr,
-                       const int* run_if = nullptr, int tile_first = 0, int tile_step = 1) {
+                       h3d_stream_t stream_, int* ovf = nullptr, const int* run_if = nullptr, int tile_first = 0, int tile_step = 1) {
     H3D_REQUIRE(stream && tables && desc && rgb, "h3d_synthesis_x3: null pointer");
     H3D_REQUIRE(h3d::aligned16(stream) && h3d::aligned16(tables), "h3d_synthesis_x3: stream/tables must be 16-byte aligned");
     H3D_REQUIRE(desc->n_blocks >= 1 && desc->n_blocks <= H3D_MAX_BLOCKS, "h3d_synthesis_x3: n_blocks=%d", desc->n_blocks);
@@ -796,8 +771,8 @@ static int synthesis_x(bool x2, const void* stream, int64_t total_stages, const 
     int mid_marked = 0, mid_total = 0;
     for (int k = n_pixel_blocks; k < first_skip; ++k)
         for (int s = 0; s < 2; ++s) { ++mid_total; mid_marked += desc->block[k].spade[s].g_offset == 1; }
-    H3D_REQUIRE(mid_marked == 0 || (x2 && mid_marked == mid_total && !load_state && !store_state),
-                "h3d_synthesis_x2: %d of %d middle-block convolutions are marked for the x3 format (all or none; single-launch x2 plans only)",
+    H3D_REQUIRE(mid_marked == 0 || (x2 && mid_marked == mid_total),
+                "h3d_synthesis_x2: %d of %d middle-block convolutions are marked for the x3 format (all or none; x2 plans only)",
                 mid_marked, mid_total);
     H3D_REQUIRE(want == total_stages, "h3d_synthesis_x3: stream has %lld stages, descriptor needs %lld",
                 (long long)total_stages, (long long)want);
@@ -808,19 +783,17 @@ static int synthesis_x(bool x2, const void* stream, int64_t total_stages, const 
         return H3D_EUNSUPPORTED;
     }
     H3D_REQUIRE(!any_const || ab, "h3d_synthesis_x3: ab table missing");
-    H3D_REQUIRE(store_state || desc->block[desc->n_blocks - 1].to_rgb || (x2 && desc->block[desc->n_blocks - 1].spade[1].b_conv >= 0),
+    H3D_REQUIRE(desc->block[desc->n_blocks - 1].to_rgb || (x2 && desc->block[desc->n_blocks - 1].spade[1].b_conv >= 0),
                 "h3d_synthesis_x3: the last block must feed ToRGB");
     for (int k = 0; k < desc->n_blocks; ++k) {
         const int64_t ho = desc->block[k].spade[1].b_conv;       // x2 plans: the ToRGB head table of a skip block (floats into `tables`)
         if (ho < 0) continue;
-        H3D_REQUIRE(x2 && !load_state && !store_state && desc->block[k].skip && !desc->block[k].to_rgb && (ho & 3) == 0 &&
+        H3D_REQUIRE(x2 && desc->block[k].skip && !desc->block[k].to_rgb && (ho & 3) == 0 &&
                         ho + (int64_t)2 * NT * 64 <= table_floats,
                     "h3d_synthesis_x2: bad ToRGB head table of block %d (offset %lld)", k, (long long)ho);
     }
-    H3D_REQUIRE((!load_state && !store_state) || (state && h3d::aligned16(state)), "h3d_synthesis_x3: state buffer missing");
     if (B == 0) return H3D_OK;
     Args A{};
-    A.state = state; A.load_state = load_state; A.store_state = store_state;
     A.ovf = ovf; A.run_if = run_if;
     A.mid_x3 = mid_marked > 0;
     H3D_REQUIRE(tile_first >= 0 && tile_step >= 1, "h3d_synthesis_x3: tile subset (%d, %d)", tile_first, tile_step);
@@ -830,7 +803,7 @@ static int synthesis_x(bool x2, const void* stream, int64_t total_stages, const 
     A.table_floats = table_floats; A.total_stages = (int)total_stages; A.g_channels = g_channels; A.Hr = Hr; A.Wr = Wr;
     if (!any_pixel) A.g_channels = 0;
     A.n_cst = n_cst; A.n_ab = n_ab; A.H = H; A.W = W; A.C = desc->C; A.HdP = NT * 32; A.first_skip = first_skip; A.n_pixel_blocks = n_pixel_blocks;
-    for (int k = 0; k < desc->n_blocks; ++k) A.heads = A.heads || desc->block[k].spade[1].b_conv >= 0;      // validated above: x2, single launch
+    for (int k = 0; k < desc->n_blocks; ++k) A.heads = A.heads || desc->block[k].spade[1].b_conv >= 0;      // validated above: x2
     const int extra = x2 ? 1 : 0;                                      // x2 keeps one more ring buffer (WeightRing LAG = 1)
     const bool deep = lds_bytes(A, NT, 6 + extra) <= 160 * 1024;      // deepest weight ring the tables leave room for
     if (lds_bytes(A, NT, kRingDepth + extra) > 160 * 1024) {
@@ -852,16 +825,16 @@ static int synthesis_x(bool x2, const void* stream, int64_t total_stages, const 
 extern "C" int h3d_synthesis_x3(const void* stream, int64_t total_stages, const float* tables, int table_floats,
                                 const h3d_synth_desc* desc, const float* G, int g_channels, int Hr, int Wr,
                                 const float* cst, int n_cst, const float* ab, int n_ab, float* rgb, int B, int H, int W,
-                                float* state, int load_state, int store_state, h3d_stream_t stream_) {
+                                h3d_stream_t stream_) {
     return synthesis_x(false, stream, total_stages, tables, table_floats, desc, G, g_channels, Hr, Wr, cst, n_cst, ab, n_ab, rgb, B, H, W,
-                       state, load_state, store_state, stream_);
+                       stream_);
 }
 extern "C" int h3d_synthesis_x2(const void* stream, int64_t total_stages, const float* tables, int table_floats,
                                 const h3d_synth_desc* desc, const float* G, int g_channels, int Hr, int Wr,
                                 const float* cst, int n_cst, const float* ab, int n_ab, float* rgb, int B, int H, int W,
-                                float* state, int load_state, int store_state, h3d_stream_t stream_) {
+                                h3d_stream_t stream_) {
     return synthesis_x(true, stream, total_stages, tables, table_floats, desc, G, g_channels, Hr, Wr, cst, n_cst, ab, n_ab, rgb, B, H, W,
-                       state, load_state, store_state, stream_);
+                       stream_);
 }
 /* Range-guarded pair (round 4).  h3d_synthesis_x2_guarded is h3d_synthesis_x2 that also ORs 1 into *overflow (device memory,
  * zeroed by the caller) when any activation it converted to the f16 planes was >= 2^15 in magnitude or non-finite -- its image
@@ -874,7 +847,7 @@ extern "C" int h3d_synthesis_x2_guarded(const void* stream, int64_t total_stages
                                         int* overflow, h3d_stream_t stream_) {
     H3D_REQUIRE(overflow, "h3d_synthesis_x2_guarded: null flag");
     return synthesis_x(true, stream, total_stages, tables, table_floats, desc, G, g_channels, Hr, Wr, cst, n_cst, ab, n_ab, rgb, B, H, W,
-                       nullptr, 0, 0, stream_, overflow, nullptr);
+                       stream_, overflow, nullptr);
 }
 extern "C" int h3d_synthesis_x3_if(const void* stream, int64_t total_stages, const float* tables, int table_floats,
                                    const h3d_synth_desc* desc, const float* G, int g_channels, int Hr, int Wr,
@@ -882,7 +855,7 @@ extern "C" int h3d_synthesis_x3_if(const void* stream, int64_t total_stages, con
                                    const int* run_if, h3d_stream_t stream_) {
     H3D_REQUIRE(run_if, "h3d_synthesis_x3_if: null flag");
     return synthesis_x(false, stream, total_stages, tables, table_floats, desc, G, g_channels, Hr, Wr, cst, n_cst, ab, n_ab, rgb, B, H, W,
-                       nullptr, 0, 0, stream_, nullptr, run_if);
+                       stream_, nullptr, run_if);
 }
 /* Sampled error monitor of the x2 engine (round 5).  h3d_synthesis_x3_tiles is h3d_synthesis_x3 restricted to the 128-pixel
  * tiles tile_first, tile_first + tile_step, .. of every sample: it writes those pixels of `rgb` (a scratch image of the full
@@ -892,7 +865,7 @@ extern "C" int h3d_synthesis_x3_tiles(const void* stream, int64_t total_stages, 
                                       const float* cst, int n_cst, const float* ab, int n_ab, float* rgb, int B, int H, int W,
                                       int tile_first, int tile_step, h3d_stream_t stream_) {
     return synthesis_x(false, stream, total_stages, tables, table_floats, desc, G, g_channels, Hr, Wr, cst, n_cst, ab, n_ab, rgb, B, H, W,
-                       nullptr, 0, 0, stream_, nullptr, nullptr, tile_first, tile_step);
+                       stream_, nullptr, nullptr, tile_first, tile_step);
 }
 
 namespace {

@@ -39,6 +39,49 @@ def _pad(v, n):
     return out
 
 
+class _Table:
+    """A flat fp32 table under construction: add() appends a tensor and returns its offset in floats.  align = 4 pads every
+    entry to whole float4s (the x3 / x3t kernels read their tables 16 bytes at a time), align = 1 leaves the fp32 engine's blob
+    as it is."""
+
+    def __init__(self, align):
+        self.align, self.chunks, self.floats = align, [], 0
+
+    def add(self, t):
+        o = self.floats
+        t = t.flatten().float()
+        pad = (-t.numel()) % self.align
+        if pad:
+            t = torch.cat([t, t.new_zeros(pad)])
+        self.chunks.append(t)
+        self.floats += t.numel()
+        return o
+
+    def cat(self):
+        return torch.cat(self.chunks).contiguous()
+
+
+def _add_coord_input(tab, desc, w_in, b_in, HdP):
+    """The coordinate input's tables: w_in [C, 2] as two vectors, b_in; their offsets go into the descriptor."""
+    desc.w_in = tab.add(torch.cat([_pad(w_in[:, 0], HdP), _pad(w_in[:, 1], HdP)]))
+    desc.b_in = tab.add(_pad(b_in, HdP))
+
+
+def _rgb_table(wr, br, HdP):
+    """A ToRGB layer's table: the three weight rows padded to HdP, then the bias padded to 4."""
+    return torch.cat([_pad(wr[0], HdP), _pad(wr[1], HdP), _pad(wr[2], HdP), _pad(br, 4)])
+
+
+def _copy_layout(src, dst):
+    """The fields of the base descriptor that every engine's descriptor shares: per block skip / to_rgb, per SPADE its style
+    kind and its indices into the per-forward tables."""
+    for k in range(src.n_blocks):
+        dst.block[k].skip, dst.block[k].to_rgb = src.block[k].skip, src.block[k].to_rgb
+        for s in range(2):
+            d, so = dst.block[k].spade[s], src.block[k].spade[s]
+            d.pixel_style, d.g_offset, d.cst_index, d.ab_index = so.pixel_style, so.g_offset, so.cst_index, so.ab_index
+
+
 class SpadeDesc(ctypes.Structure):
     _fields_ = [("pixel_style", ctypes.c_int32), ("g_offset", ctypes.c_int32), ("cst_index", ctypes.c_int32),
                 ("ab_index", ctypes.c_int32), ("w_gamma", ctypes.c_int64), ("w_beta", ctypes.c_int64),
@@ -72,23 +115,15 @@ class SynthesisPlan:
         HdP = (C + 31) // 32 * 32
         self.HdP = HdP
         NT, KBH = HdP // 32, HdP // 8
-        chunks, off = [], [0]
-
-        def add(t):
-            o = off[0]
-            chunks.append(t)
-            off[0] += t.numel()
-            return o
-
+        tab = _Table(1)
+        add = tab.add
         desc = SynthDesc()
         desc.n_blocks, desc.C = n_blocks, C
-        w_in = g(f"{input_prefix}.network.0.weight").reshape(C, 2)
-        desc.w_in = add(torch.cat([_pad(w_in[:, 0], HdP), _pad(w_in[:, 1], HdP)]))
-        desc.b_in = add(_pad(g(f"{input_prefix}.network.0.bias"), HdP))
+        self._w_in, self._b_in = g(f"{input_prefix}.network.0.weight").reshape(C, 2), g(f"{input_prefix}.network.0.bias")
+        _add_coord_input(tab, desc, self._w_in, self._b_in, HdP)
         ws_all, bs_all, self.pixel_ids, self.const_ids = [], [], [], []
         self._raw = []          # per SPADE: dict of dense fp32 tensors (consumed by the x3 builder)
         self._rgb = {}
-        self._w_in, self._b_in = w_in, g(f"{input_prefix}.network.0.bias")
         wg_c, bg_c, wb_c, bb_c, sc_c, sh_c = [], [], [], [], [], []
         for k in range(n_blocks):
             pixel = map3d_mode == "all" or k in mod_blocks
@@ -132,9 +167,9 @@ class SynthesisPlan:
                 tr = f"{prefix}.to_rgbs.m3d_{k}.linear"
                 wr = g(tr + ".weight").reshape(3, C)
                 self._rgb[k] = (wr, g(tr + ".bias"))
-                bd.w_rgb = add(torch.cat([_pad(wr[0], HdP), _pad(wr[1], HdP), _pad(wr[2], HdP), _pad(g(tr + ".bias"), 4)]))
+                bd.w_rgb = add(_rgb_table(*self._rgb[k], HdP))
         self.desc = desc
-        self.blob = torch.cat(chunks).contiguous()
+        self.blob = tab.cat()
         self.ws_all = torch.stack(ws_all)                                 # [2*nb, 128, F]
         self.bs_all = torch.stack(bs_all)                                 # [2*nb, 128]
         pix = torch.tensor(self.pixel_ids, dtype=torch.long, device=device)
@@ -202,10 +237,10 @@ class SynthesisPlan:
 
     def _x3_fits(self, x2):
         x3 = self.build_x3(bool(x2))           # the plan that would run: an x2 plan with ToRGB heads has its own table set
-        need = _lib.load().h3d_synthesis_x3_lds_bytes
-        heads = lambda seg: any(seg["desc"].block[j].spade[1].b_conv >= 0 for j in range(seg["desc"].n_blocks))
-        return all(need(seg["tables"].numel(), len(self.const_ids), len(self.pixel_ids), self.C,
-                        (3 if heads(seg) else 1) if x2 else 0) <= 160 * 1024 for seg in x3["segments"])
+        return self._x3_lds_bytes(x3, (3 if x3["heads"] else 1) if x2 else 0) <= 160 * 1024
+
+    def _x3_lds_bytes(self, x3, kind):
+        return _lib.load().h3d_synthesis_x3_lds_bytes(x3["tables"].numel(), len(self.const_ids), len(self.pixel_ids), self.C, kind)
 
     # |x| < 2^15 keeps both f16 planes of the x2 arithmetic finite (hi = f16(x); lo * 2^12 <= ulp(hi) * 2^11): csrc/synthesis_x3.hip
     X2_LIMIT = 32768.0
@@ -366,7 +401,8 @@ class SynthesisPlan:
         C = self.C
         NT = _lib.load().h3d_synthesis_x3t_tiles(C)
         HdP, KS = 32 * NT, 2 * NT
-        wchunks, woff, tchunks, toff = [], [0], [], [0]
+        wchunks, woff, tab = [], [0], _Table(4)
+        add_t = tab.add
 
         def add_w(w_out_in, ks, acc_order):
             o = woff[0]
@@ -378,27 +414,15 @@ class SynthesisPlan:
             woff[0] += wchunks[-1].numel() * 2
             return o
 
-        def add_t(t):
-            o = toff[0]
-            t = t.flatten().float()
-            pad = (-t.numel()) % 4
-            if pad:
-                t = torch.cat([t, t.new_zeros(pad)])
-            tchunks.append(t)
-            toff[0] += t.numel()
-            return o
-
         desc = SynthDesc()
         desc.n_blocks, desc.C = self.n_blocks, C
-        desc.w_in = add_t(torch.cat([_pad(self._w_in[:, 0], HdP), _pad(self._w_in[:, 1], HdP)]))
-        desc.b_in = add_t(_pad(self._b_in, HdP))
+        _add_coord_input(tab, desc, self._w_in, self._b_in, HdP)
+        _copy_layout(self.desc, desc)
         for k in range(self.n_blocks):
-            src, dst = self.desc.block[k], desc.block[k]
-            dst.skip, dst.to_rgb = src.skip, src.to_rgb
+            dst = desc.block[k]
             for s in range(2):
                 raw = self._raw[2 * k + s]
-                d, so = dst.spade[s], src.spade[s]
-                d.pixel_style, d.g_offset, d.cst_index, d.ab_index = so.pixel_style, so.g_offset, so.cst_index, so.ab_index
+                d = dst.spade[s]
                 if raw["pixel"]:
                     d.w_gamma = add_w(raw["wgam"], SHARED // 16, False)
                     d.w_beta = add_w(raw["wbet"], SHARED // 16, False)
@@ -407,131 +431,91 @@ class SynthesisPlan:
                 d.w_conv = add_w(raw["conv_w"], KS, True)
                 d.b_conv = add_t(_pad(raw["conv_b"], HdP))
             if dst.to_rgb:
-                wr, br = self._rgb[k]
-                dst.w_rgb = add_t(torch.cat([_pad(wr[0], HdP), _pad(wr[1], HdP), _pad(wr[2], HdP), _pad(br, 4)]))
-        self._x3t[(dtype, fmt)] = dict(desc=desc, wblob=torch.cat(wchunks).contiguous(), tables=torch.cat(tchunks).contiguous(),
-                                NT=NT, HdP=HdP)
+                dst.w_rgb = add_t(_rgb_table(*self._rgb[k], HdP))
+        self._x3t[(dtype, fmt)] = dict(desc=desc, wblob=torch.cat(wchunks).contiguous(), tables=tab.cat(), NT=NT, HdP=HdP)
         return self._x3t[(dtype, fmt)]
 
-    # Optional split of the network into several launches whose weight streams each fit the 4 MB L2 of an XCD
-    # (H3D_SYNTH_SEGMENT_BYTES=2359296).  Measured on MI355X: the single-launch stream (6.3 MB, 63 % L2 hit rate) is
-    # FASTER than three L2-resident segments (74 vs 82 ms) -- the misses are served by the Infinity Cache and the
-    # kernel is not bound by them -- so segmentation is off by default.
-    X3_SEGMENT_BYTES = int(os.environ.get("H3D_SYNTH_SEGMENT_BYTES", 1 << 40))
-
     def build_x3(self, x2=False):
-        """Segments of consecutive blocks whose weight streams each stay well inside the 4 MB L2 of an XCD; each
-        segment carries its own descriptor, fp32 tables and bf16 hi/lo stream (x2: f16 hi fragments + fp6 records)."""
+        """The plan of the register engine: its descriptor, fp32 tables and one weight stream in consumption order (bf16 hi/lo
+        stages; x2: f16 hi fragments + fp6 records).  x2 plans carry the ToRGB head tables (_torgb_heads) when X2_HEADS asks
+        for them and they fit: plan["heads"] says whether they are there."""
         cache = "_x2" if x2 else "_x3"
-        if getattr(self, cache, None) is not None:
-            return getattr(self, cache)
+        if getattr(self, cache) is None:
+            plan = self._build_x3(x2, x2 and self.X2_HEADS)
+            # the head tables are 4 KB per skip block (minus the 3 KB zero table): a plan they push past the 160 KB of LDS keeps
+            # the riding ToRGB instead (the kernel would refuse the launch, and the plan would otherwise fall to the x3 engine)
+            if plan["heads"] and self._x3_lds_bytes(plan, 3) > 160 * 1024:
+                plan = self._build_x3(x2, False)
+            setattr(self, cache, plan)
+        return getattr(self, cache)
+
+    def _build_x3(self, x2, heads):
         pack = self.pack_stream_x2 if x2 else self.pack_stream_bf16
         C = self.C
         NT = 8 if C > 128 else 4
         HdP = NT * 32
-        stage_bytes = NT * 2048
-        # greedy partition of the blocks by stream size
-        blk_stages = []
-        for k in range(self.n_blocks):
-            n = 0
-            for s in range(2):
-                n += (2 * (SHARED // 16) if self._raw[2 * k + s]["pixel"] else 0) + 2 * NT
-            blk_stages.append(n)
-        ranges, cur, cur_bytes = [], [], 0
-        for k, n in enumerate(blk_stages):
-            if cur and cur_bytes + n * stage_bytes > self.X3_SEGMENT_BYTES:
-                ranges.append(cur)
-                cur, cur_bytes = [], 0
-            cur.append(k)
-            cur_bytes += n * stage_bytes
-        ranges.append(cur)
         # Conv biases are folded on the host (the x3 kernel never adds one): the kernel's activations are the true ones
         # minus a per-channel "carry" -- the bias of the conv that produced them plus, along a skip chain, the carry of
         # the block input.  Every consumer is affine in its input, so the carry moves into its shift:
         #   SPADE  y = lrelu(sc * (x + c) + sh)  ->  sh' = sh + sc * c      (per-sample ab tables: run(); vec: here)
         #   ToRGB  rgb += Wr (x + c) + br        ->  br' = br + Wr c
-        segments = []
         carry = torch.zeros(HdP, device=self.device, dtype=torch.float32)
         ab_carry = torch.zeros(max(1, len(self.const_ids)), HdP, device=self.device, dtype=torch.float32)
-        for blocks in ranges:
-            chunks, off = [], [0]
+        tab = _Table(4)
+        desc = SynthDesc()
+        desc.n_blocks, desc.C = self.n_blocks, C
+        _add_coord_input(tab, desc, self._w_in, self._b_in, HdP)
+        _copy_layout(self.desc, desc)
+        stream, stages = [], 0
+        rgb_tables = {}                                         # block k -> (Wr [3, C], br' [3]) as written to the tables
+        for k in range(self.n_blocks):
+            src = self.desc.block[k]
+            c_in = carry
+            # the constant-style blocks between the per-pixel blocks and the first skip block (block 3 of the shipped configs)
+            mid_block = (not src.skip and not any(self.desc.block[q].skip for q in range(k))
+                         and not self._raw[2 * k]["pixel"] and not self._raw[2 * k + 1]["pixel"])
+            for s in range(2):
+                raw = self._raw[2 * k + s]
+                d = desc.block[k].spade[s]
+                if raw["pixel"]:
+                    stream.append(pack(raw["wgam"], SHARED // 16, NT))
+                    stream.append(pack(raw["wbet"], SHARED // 16, NT))
+                    stages += 2 * (SHARED // 16)
+                    sc, sh = _pad(raw["sc"], HdP), _pad(raw["sh"], HdP)
+                    d.vec = tab.add(torch.cat([_pad(raw["bgam"] + 1.0, HdP), _pad(raw["bbet"], HdP), sc, sh + sc * carry]))
+                else:
+                    ab_carry[d.ab_index] = carry
+                if x2 and self.X2_MID_X3 and mid_block:
+                    # round 6: this convolution on three bf16 products inside the x2 kernel (csrc/synthesis_x3.hip: MIDX3): its
+                    # stages in the x3 format, the SPADE marked through its (otherwise unused) g_offset
+                    stream.append(self.pack_stream_bf16(raw["conv_w"], 2 * NT, NT))
+                    d.g_offset = 1
+                else:
+                    stream.append(pack(raw["conv_w"], 2 * NT, NT))
+                stages += 2 * NT
+                d.b_conv = -1                                   # folded: the kernel has no bias add
+                carry = _pad(raw["conv_b"], HdP)
+                if s == 1 and src.skip:
+                    carry = carry + c_in
+            if src.to_rgb:
+                wr, br = self._rgb[k]
+                rgb_tables[k] = (wr.float(), br.float() + wr.float() @ carry[: wr.shape[1]])
+        # ToRGB tables: one per block -- or, x2 plans with heads, the head tiles of the skip blocks (_torgb_heads), which replace
+        # the tables of the skip blocks and of the block in front of them (the LDS has no room for both)
+        merged = self._torgb_heads(desc, rgb_tables, tab, NT, HdP) if heads else ()
+        for k, (wr, br) in rgb_tables.items():
+            if k not in merged:
+                desc.block[k].w_rgb = tab.add(_rgb_table(wr, br, HdP))
+        return dict(desc=desc, tables=tab.cat(), stream=torch.cat(stream).contiguous(), stages=stages, NT=NT, HdP=HdP,
+                    ab_carry=ab_carry, heads=bool(merged))
 
-            def add(t):
-                o = off[0]
-                t = t.flatten().float()
-                pad = (-t.numel()) % 4
-                if pad:
-                    t = torch.cat([t, t.new_zeros(pad)])
-                chunks.append(t)
-                off[0] += t.numel()
-                return o
-
-            desc = SynthDesc()
-            desc.n_blocks, desc.C = len(blocks), C
-            desc.w_in = add(torch.cat([_pad(self._w_in[:, 0], HdP), _pad(self._w_in[:, 1], HdP)]))
-            desc.b_in = add(_pad(self._b_in, HdP))
-            stream, stages = [], 0
-            rgb_tables = {}                                         # block j of this segment -> (Wr [3, C], br' [3]) as written to the tables
-            for j, k in enumerate(blocks):
-                src, dst = self.desc.block[k], desc.block[j]
-                dst.skip, dst.to_rgb = src.skip, src.to_rgb
-                c_in = carry
-                # the constant-style blocks between the per-pixel blocks and the first skip block (block 3 of the shipped configs)
-                mid_block = (not src.skip and not any(self.desc.block[q].skip for q in range(k))
-                             and not self._raw[2 * k]["pixel"] and not self._raw[2 * k + 1]["pixel"] and len(ranges) == 1)
-                for s in range(2):
-                    raw = self._raw[2 * k + s]
-                    d, so = dst.spade[s], src.spade[s]
-                    d.pixel_style, d.g_offset, d.cst_index, d.ab_index = so.pixel_style, so.g_offset, so.cst_index, so.ab_index
-                    if raw["pixel"]:
-                        stream.append(pack(raw["wgam"], SHARED // 16, NT))
-                        stream.append(pack(raw["wbet"], SHARED // 16, NT))
-                        stages += 2 * (SHARED // 16)
-                        sc, sh = _pad(raw["sc"], HdP), _pad(raw["sh"], HdP)
-                        d.vec = add(torch.cat([_pad(raw["bgam"] + 1.0, HdP), _pad(raw["bbet"], HdP), sc, sh + sc * carry]))
-                    else:
-                        ab_carry[so.ab_index] = carry
-                    if x2 and self.X2_MID_X3 and mid_block:
-                        # round 6: this convolution on three bf16 products inside the x2 kernel (csrc/synthesis_x3.hip: MIDX3): its
-                        # stages in the x3 format, the SPADE marked through its (otherwise unused) g_offset
-                        stream.append(self.pack_stream_bf16(raw["conv_w"], 2 * NT, NT))
-                        d.g_offset = 1
-                    else:
-                        stream.append(pack(raw["conv_w"], 2 * NT, NT))
-                    stages += 2 * NT
-                    d.b_conv = -1                                   # folded: the kernel has no bias add
-                    carry = _pad(raw["conv_b"], HdP)
-                    if s == 1 and src.skip:
-                        carry = carry + c_in
-                if dst.to_rgb:
-                    wr, br = self._rgb[k]
-                    br = br.float() + wr.float() @ carry[: wr.shape[1]]
-                    rgb_tables[j] = (wr.float(), br)
-            # ToRGB tables: one per block -- or, x2 single-launch plans, the head tiles of the skip blocks (_torgb_heads), which
-            # replace the tables of the skip blocks and of the block in front of them (the LDS has no room for both)
-            merged = self._torgb_heads(desc, blocks, rgb_tables, add, NT, HdP) if (x2 and self.X2_HEADS and len(ranges) == 1) else ()
-            for j, (wr, br) in rgb_tables.items():
-                if j not in merged:
-                    desc.block[j].w_rgb = add(torch.cat([_pad(wr[0], HdP), _pad(wr[1], HdP), _pad(wr[2], HdP), _pad(br, 4)]))
-            segments.append(dict(desc=desc, tables=torch.cat(chunks).contiguous(), stream=torch.cat(stream).contiguous(),
-                                 stages=stages, blocks=blocks))
-        if x2 and self.X2_HEADS and len(ranges) == 1:
-            # the head tables are 4 KB per skip block (minus the 3 KB zero table): a plan they push past the 160 KB of LDS keeps
-            # the riding ToRGB instead (the kernel would refuse the launch, and the plan would otherwise fall to the x3 engine)
-            seg = segments[0]
-            if any(seg["desc"].block[j].spade[1].b_conv >= 0 for j in range(seg["desc"].n_blocks)) and \
-                    _lib.load().h3d_synthesis_x3_lds_bytes(seg["tables"].numel(), len(self.const_ids), len(self.pixel_ids), self.C, 3) > 160 * 1024:
-                self.X2_HEADS = False
-                return self.build_x3(True)
-        setattr(self, cache, dict(segments=segments, HdP=HdP, NT=NT, state=None, ab_carry=ab_carry))
-        return getattr(self, cache)
-
+    # Requests (the outcome is build_x3(True)["heads"]): ToRGB head tables in x2 plans
     X2_HEADS = os.environ.get("H3D_SYNTH_HEADS", "1") != "0"
     # x2 plans: the base of the residual stream (the constant-style block in front of the first skip block) on three bf16 products
     # -- the per-contraction attribution's largest contributor (b3.conv1 4.8e-4, b3.conv0 2.3e-4 of an all-x2 7.9e-4)
     X2_MID_X3 = os.environ.get("H3D_SYNTH_MID_X3", "1") != "0"
 
-    def _torgb_heads(self, desc, blocks, rgb_tables, add, NT, HdP):
+    def _torgb_heads(self, desc, rgb_tables, tab, NT, HdP):
         """x2 register engine, round 5: the ToRGB layers of the skip blocks as a NINTH output tile of each block's second
         convolution (csrc/synthesis_x3.hip: conv_progressive HEAD).  With x_k = x_{k-1} + W1_k y_k along the skip chain (biases
         live in the carries, build_x3), sum_k Wr_k x_k over the skip blocks k >= fs that feed ToRGB is
@@ -543,31 +527,32 @@ class SynthesisPlan:
         M_j travels as a 4 KB table per block, [k-step][f16 hi fragment | half of the fp6 record][4 rows x 2 lane halves][16 B] --
         the 8 lanes (rows 0-3, both halves) of a one-tile x2 stream of M_j padded to 32 rows -- at the float offset stored in the
         block's spade[1].b_conv (unused by this engine otherwise: biases are folded); the skip blocks' to_rgb flags are cleared."""
-        fs = next((j for j in range(len(blocks)) if desc.block[j].skip), None)
-        if fs is None or fs == 0 or not any(j in rgb_tables for j in range(fs, len(blocks))):
+        n = desc.n_blocks
+        fs = next((j for j in range(n) if desc.block[j].skip), None)
+        if fs is None or fs == 0 or not any(j in rgb_tables for j in range(fs, n)):
             return ()
         C = self.C
         V = torch.zeros(3, C, dtype=torch.float64, device=self.device)
         bias = torch.zeros(3, dtype=torch.float64, device=self.device)
         heads = {}
-        for j in range(len(blocks) - 1, fs - 1, -1):
+        for j in range(n - 1, fs - 1, -1):
             if j in rgb_tables:
                 V = V + rgb_tables[j][0].double()
                 bias = bias + rgb_tables[j][1].double()
-            w1 = self._raw[2 * blocks[j] + 1]["conv_w"].double()                      # [C_out, C_in] of the block's second convolution
+            w1 = self._raw[2 * j + 1]["conv_w"].double()                              # [C_out, C_in] of the block's second convolution
             heads[j] = V @ w1                                                          # [3, C_in]
         # entry term: block fs - 1's table takes (its own ToRGB, if any) + V x_{fs-1} and every later bias
         w0, b0 = rgb_tables.get(fs - 1, (torch.zeros(3, C, device=self.device), torch.zeros(3, device=self.device)))
         wm, bm = (w0.double() + V).float(), (b0.double() + bias).float()
         desc.block[fs - 1].to_rgb = 1
-        desc.block[fs - 1].w_rgb = add(torch.cat([_pad(wm[0], HdP), _pad(wm[1], HdP), _pad(wm[2], HdP), _pad(bm, 4)]))
+        desc.block[fs - 1].w_rgb = tab.add(_rgb_table(wm, bm, HdP))
         lanes = torch.tensor([0, 1, 2, 3, 32, 33, 34, 35], device=self.device)
-        for j in range(fs, len(blocks)):
+        for j in range(fs, n):
             st = self.pack_stream_x2(heads[j].float(), 2 * NT, 1, acc_order=True, dense=False)            # [KS][1][2][64][8] int16
-            tab = st.view(2 * NT, 2, 64, 8)[:, :, lanes].contiguous()                                     # [KS][hi | rec][8 lanes][16 B]
+            head = st.view(2 * NT, 2, 64, 8)[:, :, lanes].contiguous()                                    # [KS][hi | rec][8 lanes][16 B]
             desc.block[j].to_rgb = 0
-            desc.block[j].spade[1].b_conv = add(tab.view(torch.float32))
-        return set(range(fs - 1, len(blocks)))               # blocks whose own ToRGB table is superseded
+            desc.block[j].spade[1].b_conv = tab.add(head.view(torch.float32))
+        return set(range(fs - 1, n))               # blocks whose own ToRGB table is superseded
 
     def per_forward_tables(self, feature_maps, fixed_style, HdP=None):
         """feature_maps [B,R,F] (rendered, channels last), fixed_style [B,F] -> (G, cst, ab)."""
@@ -622,96 +607,93 @@ class SynthesisPlan:
             ab = ab.view(Bq, nq, 2, Hq // 2, 2).permute(0, 1, 3, 2, 4).contiguous()
         return G, cst, ab
 
+    def _resolve(self, H, W, Hr, Wr):
+        """-> (family, plan, tier) that run() launches for this geometry: "x3" (the register engines, plan = build_x3), "x3t"
+        (the LDS-resident engine, plan = build_x3t of `tier`) or "f32" (the fp32 engine on self.blob, plan None)."""
+        if self.engine not in ("bf16x3", "f16x2", "f32") and self.engine not in self.X3T_TIERS:
+            raise ValueError(f"unknown synthesis engine {self.engine!r}")
+        name = self.engine
+        if name in ("bf16x3", "f16x2"):
+            x3 = self.build_x3(name == "f16x2")
+            if not self.pixel_ids or _lib.load().h3d_synthesis_x3_geometry_ok(H, W, Hr, Wr):
+                return "x3", x3, None
+            # the x3 engine's matrix-core resize does not cover this geometry: the LDS-resident engine does
+            # (f16x2 falls back to the x2 tier of that engine, bf16x3 to its three-product tier)
+            name = ("f16x2t" if name == "f16x2" else "bf16x3t") if self.x3t_supported() else "f32"
+        if name == "f32":
+            return "f32", None, None
+        tier = self.X3T_TIERS[name]
+        return "x3t", self.build_x3t(tier[0], tier[3]), tier
+
+    def _args(self, plan, G, cst, ab, rgb, B, Hr, Wr, H, W):
+        """The arguments every x3 (stream, stages, tables, table floats, ..) and x3t (weight blob, tables, ..) entry point starts
+        with, up to the image and its shape."""
+        head = ((_lib.ptr(plan["stream"]), plan["stages"], _lib.ptr(plan["tables"]), plan["tables"].numel()) if "stream" in plan
+                else (_lib.ptr(plan["wblob"]), _lib.ptr(plan["tables"])))
+        return head + (ctypes.byref(plan["desc"]), _lib.ptr(G), self.g_channels, Hr, Wr, _lib.ptr(cst), len(self.pixel_ids),
+                       _lib.ptr(ab), len(self.const_ids), _lib.ptr(rgb), B, H, W)
+
     def run(self, feature_maps, fixed_style, render_hw, out_hw, owner=None):
         """-> rgb [B,3,H,W]."""
         B = fixed_style.shape[0]
         Hr, Wr = render_hw
         H, W = out_hw
-        if self.engine not in ("bf16x3", "f16x2", "f32") and self.engine not in self.X3T_TIERS:
-            raise ValueError(f"unknown synthesis engine {self.engine!r}")
-        x2 = self.engine == "f16x2"
-        x3 = self.build_x3(x2) if self.engine in ("bf16x3", "f16x2") else None
-        tier = self.X3T_TIERS.get(self.engine, self.X3T_TIERS["bf16x3t"])
-        x3t = self.build_x3t(tier[0], tier[3]) if self.engine in self.X3T_TIERS else None
-        if x3 and self.pixel_ids and not _lib.load().h3d_synthesis_x3_geometry_ok(H, W, Hr, Wr):
-            # the x3 engine's matrix-core resize does not cover this geometry: the LDS-resident engine does
-            # (f16x2 falls back to the x2 tier of that engine, bf16x3 to its three-product tier)
-            tier = self.X3T_TIERS["f16x2t" if x2 else "bf16x3t"]
-            x3, x3t = None, (self.build_x3t(tier[0], tier[3]) if self.x3t_supported() else None)
+        family, plan, tier = self._resolve(H, W, Hr, Wr)
+        x2 = family == "x3" and self.engine == "f16x2"
         with stage(owner, "synthesis_tables"):
-            if x3:
+            if family == "x3":
                 G, cst, ab = self.x3_forward_tables(feature_maps.float(), fixed_style.float(), x2)
             else:
-                G, cst, ab = self.per_forward_tables(feature_maps.float(), fixed_style.float(), x3t["HdP"] if x3t else None)
+                G, cst, ab = self.per_forward_tables(feature_maps.float(), fixed_style.float(), plan["HdP"] if plan else None)
         rgb = torch.empty(B, 3, H, W, device=fixed_style.device, dtype=torch.float32)
-        what = ("h3d_synthesis_x2" if x2 else "h3d_synthesis_x3") if x3 else "h3d_synthesis_x3t" if x3t else "h3d_synthesis"
+        what = {"x3": "h3d_synthesis_x2" if x2 else "h3d_synthesis_x3", "x3t": "h3d_synthesis_x3t", "f32": "h3d_synthesis"}[family]
+        lib, st = _lib.load(), _lib.stream_handle()
+        args = lambda p, img=rgb: self._args(p, G, cst, ab, img, B, Hr, Wr, H, W)
         with stage(owner, "synthesis"):
-            if x3t and tier[2] == 4 and self.x2_guard:
+            if family == "x3t" and tier[2] == 4 and self.x2_guard:
                 # the x2 tier of the LDS-resident engine, range-guarded like the register engine below: the bf16 tier runs
                 # behind it on the same flag and only does work when the x2 launch left its f16 range
                 alt_tier = self.X3T_TIERS["bf16x3t"]
                 alt = self.build_x3t(alt_tier[0], alt_tier[3])
-                self._flags(B, fixed_style.device)
-                call = lambda blk, tr: _lib.load().h3d_synthesis_x3t_tier_guarded(
-                    _lib.ptr(blk["wblob"]), _lib.ptr(blk["tables"]), ctypes.byref(blk["desc"]), _lib.ptr(G), self.g_channels, Hr, Wr,
-                    _lib.ptr(cst), len(self.pixel_ids), _lib.ptr(ab), len(self.const_ids), _lib.ptr(rgb), B, H, W, tr[1], tr[2],
-                    _lib.ptr(self._x2_flag), _lib.stream_handle())
-                rc = call(x3t, tier) or call(alt, alt_tier)
-            elif x3t:
-                rc = _lib.load().h3d_synthesis_x3t_tier(_lib.ptr(x3t["wblob"]), _lib.ptr(x3t["tables"]),
-                                                      ctypes.byref(x3t["desc"]), _lib.ptr(G), self.g_channels, Hr, Wr,
-                                                      _lib.ptr(cst), len(self.pixel_ids), _lib.ptr(ab), len(self.const_ids),
-                                                      _lib.ptr(rgb), B, H, W, tier[1], tier[2], _lib.stream_handle())
-            elif x3:
-                segs = x3["segments"]
-                state = None
-                if len(segs) > 1:
-                    need = B * ((H * W + 127) // 128) * 4 * (x3["NT"] * 4 + 1) * 64 * 4
-                    if x3["state"] is None or x3["state"].numel() < need:
-                        x3["state"] = torch.empty(need, device=fixed_style.device, dtype=torch.float32)
-                    state = x3["state"]
-                lib, rc = _lib.load(), 0
-                entry = lib.h3d_synthesis_x2 if x2 else lib.h3d_synthesis_x3
-                if x2 and self.x2_guard and len(segs) == 1 and state is None:
-                    # Range-guarded x2: the kernel raises an item's device flag when an activation of that item leaves the range
-                    # its f16 planes carry (|x| >= 2^15, inf, NaN upstream); the bf16 engine, launched right behind it on the same
-                    # stream, skips the items whose flag is clear and recomputes the others.  No host synchronisation; the x3
-                    # stream shares descriptor, tables and per-forward tables with the x2 one (only the weight format differs).
-                    seg, alt = segs[0], self.build_x3(False)["segments"][0]
-                    self._flags(B, fixed_style.device)
-                    common = lambda sg: (_lib.ptr(sg["stream"]), sg["stages"], _lib.ptr(sg["tables"]), sg["tables"].numel(),
-                                         ctypes.byref(sg["desc"]), _lib.ptr(G), self.g_channels, Hr, Wr, _lib.ptr(cst),
-                                         len(self.pixel_ids), _lib.ptr(ab), len(self.const_ids), _lib.ptr(rgb), B, H, W,
-                                         _lib.ptr(self._x2_flag), _lib.stream_handle())
-                    rc = lib.h3d_synthesis_x2_guarded(*common(seg))
-                    if not rc and self.x2_monitor:
-                        what = "h3d_synthesis_x3_tiles / h3d_synthesis_check"
-                        first, step = self.monitor_tiles(H, W)
-                        buf = self._x2_monitor_buf
-                        if buf is None or buf[0].shape != rgb.shape or buf[0].device != rgb.device:
-                            buf = (torch.empty_like(rgb), torch.zeros(B, device=rgb.device, dtype=torch.float32),
-                                   torch.zeros(6 * B, device=rgb.device, dtype=torch.float32))
-                            self._x2_monitor_buf = buf
-                        rc = lib.h3d_synthesis_x3_tiles(*common(alt)[:13], _lib.ptr(buf[0]), B, H, W, first, step, _lib.stream_handle())
-                        rc = rc or lib.h3d_synthesis_check(_lib.ptr(rgb), _lib.ptr(buf[0]), B, H, W, first, step,
-                                                           self.x2_monitor_tol, _lib.ptr(self._x2_flag), _lib.ptr(buf[1]),
-                                                           _lib.ptr(buf[2]), _lib.stream_handle())
-                    if not rc:
-                        what = "h3d_synthesis_x3_if"
-                        rc = lib.h3d_synthesis_x3_if(*common(alt))
-                    segs = []
-                for i, seg in enumerate(segs):
-                    rc = entry(_lib.ptr(seg["stream"]), seg["stages"], _lib.ptr(seg["tables"]),
-                                              seg["tables"].numel(), ctypes.byref(seg["desc"]), _lib.ptr(G),
-                                              self.g_channels, Hr, Wr, _lib.ptr(cst), len(self.pixel_ids), _lib.ptr(ab),
-                                              len(self.const_ids), _lib.ptr(rgb), B, H, W, _lib.ptr(state), int(i > 0),
-                                              int(i < len(segs) - 1), _lib.stream_handle())
-                    if rc:
-                        break
+                flag = _lib.ptr(self._flags(B, fixed_style.device))
+                rc = lib.h3d_synthesis_x3t_tier_guarded(*args(plan), tier[1], tier[2], flag, st) or \
+                    lib.h3d_synthesis_x3t_tier_guarded(*args(alt), alt_tier[1], alt_tier[2], flag, st)
+            elif family == "x3t":
+                rc = lib.h3d_synthesis_x3t_tier(*args(plan), tier[1], tier[2], st)
+            elif x2 and self.x2_guard:
+                # Range-guarded x2: the kernel raises an item's device flag when an activation of that item leaves the range
+                # its f16 planes carry (|x| >= 2^15, inf, NaN upstream); the bf16 engine, launched right behind it on the same
+                # stream, skips the items whose flag is clear and recomputes the others.  No host synchronisation; the x3
+                # stream shares descriptor, tables and per-forward tables with the x2 one (only the weight format differs).
+                alt = self.build_x3(False)
+                flag = _lib.ptr(self._flags(B, fixed_style.device))
+                rc = lib.h3d_synthesis_x2_guarded(*args(plan), flag, st)
+                if not rc and self.x2_monitor:
+                    what = "h3d_synthesis_x3_tiles / h3d_synthesis_check"
+                    first, step = self.monitor_tiles(H, W)
+                    buf = self._monitor_buf(rgb)
+                    rc = lib.h3d_synthesis_x3_tiles(*args(alt, buf[0]), first, step, st)
+                    rc = rc or lib.h3d_synthesis_check(_lib.ptr(rgb), _lib.ptr(buf[0]), B, H, W, first, step, self.x2_monitor_tol,
+                                                       flag, _lib.ptr(buf[1]), _lib.ptr(buf[2]), st)
+                if not rc:
+                    what = "h3d_synthesis_x3_if"
+                    rc = lib.h3d_synthesis_x3_if(*args(alt), flag, st)
+            elif family == "x3":
+                rc = (lib.h3d_synthesis_x2 if x2 else lib.h3d_synthesis_x3)(*args(plan), st)
             else:
                 rc = self._launch(G, cst, ab, rgb, B, Hr, Wr, H, W)
         _lib.check(rc, what)
         return rgb
+
+    def _monitor_buf(self, rgb):
+        """(scratch image, per-item sampled error [B], work [6 B]) of the x2 monitor, kept between runs of one shape."""
+        buf = self._x2_monitor_buf
+        if buf is None or buf[0].shape != rgb.shape or buf[0].device != rgb.device:
+            B = rgb.shape[0]
+            buf = (torch.empty_like(rgb), torch.zeros(B, device=rgb.device, dtype=torch.float32),
+                   torch.zeros(6 * B, device=rgb.device, dtype=torch.float32))
+            self._x2_monitor_buf = buf
+        return buf
 
     def _flags(self, B, device):
         """The per-item flags of a guarded run, zeroed on the current stream."""

@@ -467,13 +467,7 @@ int h3d_synthesis(const void* blob, const h3d_synth_desc* desc, const float* G, 
  * br' = br + Wr*c -- see SynthesisPlan.build_x3 in lib/generators/synthesis_pack.py).
  * Returns H3D_EUNSUPPORTED (use h3d_synthesis) for C > 256, a per-pixel-style block after the first skip block, a
  * block without skip connection after the first one that has it, or (with per-pixel-style blocks) a geometry
- * h3d_synthesis_x3_geometry_ok rejects.
- *
- * Segmented execution: the weight stream of the whole network (6.3 MB at C=256) does not fit the 4 MB L2 of an XCD,
- * so a caller may run the blocks in several launches whose streams do (desc = the blocks of one segment).  Between
- * launches the per-pixel activations and ToRGB partial sums live in `state`
- * (B * ceil(H*W/128) * 4 wave tiles * (tiles*4 + 1) * 64 float4, private lane-linear layout): store_state=1 writes
- * it instead of the image, load_state=1 resumes from it instead of generating the coordinate input. */
+ * h3d_synthesis_x3_geometry_ok rejects. */
 /* 1 when the x3 engine's matrix-core bilinear resize covers this geometry (only needed with per-pixel-style blocks):
  * W a multiple of 32 and 32 consecutive output pixels touching at most 8 low-res columns (31*Wr < 6*W). */
 int h3d_synthesis_x3_geometry_ok(int H, int W, int Hr, int Wr);
@@ -485,7 +479,7 @@ int64_t h3d_synthesis_x3_lds_bytes(int table_floats, int n_ab, int n_cst, int C,
 int h3d_synthesis_x3(const void* stream, int64_t total_stages, const float* tables, int table_floats,
                      const h3d_synth_desc* desc, const float* G, int g_channels, int Hr, int Wr,
                      const float* cst, int n_cst, const float* ab, int n_ab, float* rgb, int B, int H, int W,
-                     float* state, int load_state, int store_state, h3d_stream_t stream_handle);
+                     h3d_stream_t stream_handle);
 
 /* h3d_synthesis_x3 in the "x2" arithmetic (csrc/x3_common.hpp, see the _x2 field entry points): every conv / gamma /
  * beta contraction is one f16 product hi*hi plus one block-scaled fp6 (e2m3) matrix instruction for the two cross terms;
@@ -496,13 +490,13 @@ int h3d_synthesis_x3(const void* stream, int64_t total_stages, const float* tabl
  * h3d_synthesis_x3; the stream holds, per stage, [tile][1 KiB f16 hi fragment][1 KiB half of the K-tile's fp6 records]
  * (record layout as for h3d_field_pack_x2; SynthesisPlan.pack_stream_x2), and the kernel needs
  * h3d_synthesis_x2_extra_lds(C) more bytes of LDS than h3d_synthesis_x3 (one more ring buffer).
- * ToRGB heads (round 5, single-launch x2 plans only): a skip block whose spade[1].b_conv is >= 0 (this engine folds conv biases on
+ * ToRGB heads (round 5, x2 plans only): a skip block whose spade[1].b_conv is >= 0 (this engine folds conv biases on
  * the host, so the field is free) carries at that FLOAT offset of `tables` a 4 KB table [k-step][f16 hi fragment | half of the
  * fp6 record][4 rows x 2 lane halves][16 B] = the x2 operands of M_j = (sum of the ToRGB weights of this and every later block)
  * x W_conv1 of the block, 3 rows used: the block's second convolution multiplies it with its own input fragments as a ninth
  * output tile, accumulated over all skip blocks into the image.  Such blocks have to_rgb = 0, and the block in front of the
  * first skip block carries the summed ToRGB weights and biases (exact algebra on lib/generators/map3d_generator.py:82-86).
- * Three-product middle blocks (round 6, single-launch x2 plans only): the constant-style blocks between the per-pixel-style blocks
+ * Three-product middle blocks (round 6, x2 plans only): the constant-style blocks between the per-pixel-style blocks
  * and the first skip block (block 3 of the shipped configurations: the base of the residual stream) may carry g_offset = 1 in both
  * of their SPADEs (the field is unused for pixel_style = 0): their convolutions' stages are then in the h3d_synthesis_x3 format
  * (bf16 hi | lo) and run on three bf16 products inside this kernel -- all such blocks or none.  SynthesisPlan.build_x3(x2=True)
@@ -510,11 +504,11 @@ int h3d_synthesis_x3(const void* stream, int64_t total_stages, const float* tabl
 int h3d_synthesis_x2(const void* stream, int64_t total_stages, const float* tables, int table_floats,
                      const h3d_synth_desc* desc, const float* G, int g_channels, int Hr, int Wr,
                      const float* cst, int n_cst, const float* ab, int n_ab, float* rgb, int B, int H, int W,
-                     float* state, int load_state, int store_state, h3d_stream_t stream_handle);
+                     h3d_stream_t stream_handle);
 int h3d_synthesis_x2_extra_lds(int C);
 
 /* Range-guarded pair (round 4).  The x2 engine's operand planes are f16: hi = f16(x) and f16(lo * 2^12) with |lo| <= ulp(hi)/2
- * are finite exactly for |x| < 2^15.  h3d_synthesis_x2_guarded is h3d_synthesis_x2 (single launch: no state) that also ORs 1
+ * are finite exactly for |x| < 2^15.  h3d_synthesis_x2_guarded is h3d_synthesis_x2 that also ORs 1
  * into overflow[b] (int32[B] in device memory, zeroed by the caller on the same stream; round 6: ONE FLAG PER SAMPLE of the
  * batch, rounds 4-5 had one per launch) when any activation of sample b it fed to the matrix cores was >= 2^15 in magnitude or
  * not finite -- that sample's image is then not to be used.  h3d_synthesis_x3_if is h3d_synthesis_x3 (bf16 planes: fp32
@@ -536,7 +530,7 @@ int h3d_synthesis_x3_if(const void* stream, int64_t total_stages, const float* t
  * lib/components/map3d_layers.py:176-238, have no reduced-precision tier to watch).  The x2 arithmetic sits inside the 1e-3
  * parity budget with little room (measured over 192 images: up to 9.6e-4 of the channel maximum, median 2.2e-4), so every forward checks a
  * sample of its own output against the fp32-class engine:
- *   h3d_synthesis_x3_tiles  h3d_synthesis_x3 (single launch, `stream` in the x3 format) restricted to the 128-pixel tiles
+ *   h3d_synthesis_x3_tiles  h3d_synthesis_x3 (`stream` in the x3 format) restricted to the 128-pixel tiles
  *                           tile_first, tile_first + tile_step, .. of every sample; writes those pixels of `rgb` (a scratch
  *                           image of the full [B,3,H,W] shape) and nothing else;
  *   h3d_synthesis_check     per sample: err = max over channels of (max|rgb - rgb_ref| over exactly those tiles) / (max|rgb|

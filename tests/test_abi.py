@@ -36,6 +36,14 @@ def test_version_and_error_string(lib):
     assert isinstance(lib.h3d_last_error(), bytes)
 
 
+def test_synthesis_register_engines_take_18_arguments():
+    """One launch per network: no state buffer, no load / store flags -- in the header and in the ctypes binding alike."""
+    sig = importlib.import_module("3dhumangan_amd._lib")._SIGNATURES
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "h3d.h")).read(), flags=re.S)
+    for name in ("h3d_synthesis_x3", "h3d_synthesis_x2"):
+        assert len(re.search(name + r"\s*\(([^)]*)\)", text).group(1).split(",")) == len(sig[name][1]) == 18
+
+
 def test_argument_validation_needs_no_gpu(lib):
     """Bad arguments are rejected before any HIP call."""
     lib.h3d_ray_integrate.restype = ctypes.c_int

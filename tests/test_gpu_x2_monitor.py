@@ -100,7 +100,7 @@ def test_tile_subset_launch_writes_the_sampled_tiles_only():
     fmap, style = torch.randn(B, Hr * Wr, 128).to(DEV), torch.randn(B, 128).to(DEV)
     plan.engine = "bf16x3"
     full = plan.run(fmap, style, (Hr, Wr), (H, W))
-    seg = plan.build_x3(False)["segments"][0]
+    seg = plan.build_x3(False)
     Gt, cst, ab = plan.x3_forward_tables(fmap.float(), style.float(), False)
     scratch = torch.full_like(full, -7.0)
     first, step = 3, 5
@@ -158,14 +158,14 @@ def test_torgb_head_tiles_give_the_image_of_the_riding_torgb(width):
     fmap, style = torch.randn(2, 576, width), torch.randn(2, width)
     want = oracle_rgb(sd, meta, fmap, style)
     with_heads = run(G, meta, fmap, style)
-    desc = plan.build_x3(True)["segments"][0]["desc"]
+    desc = plan.build_x3(True)["desc"]
     assert any(desc.block[k].spade[1].b_conv >= 0 for k in range(desc.n_blocks))          # the head tables are in the plan
     assert not plan.x2_fell_back()
     plan.X2_HEADS = False
     plan._x2 = None                                                                       # rebuild without heads
     try:
         without = run(G, meta, fmap, style)
-        desc = plan.build_x3(True)["segments"][0]["desc"]
+        desc = plan.build_x3(True)["desc"]
         assert all(desc.block[k].spade[1].b_conv < 0 for k in range(desc.n_blocks))
         assert not plan.x2_fell_back()
     finally:

@@ -78,10 +78,9 @@ def emulate(plan, fmap_lowres, fixed_style, Hr, Wr, H, W, x2=False):
     """float64 restatement of synthesis_x3_kernel on the plan's own tables / stream (x2: the x2 arithmetic on the decoded f16
     fragments and fp6 records, with the per-pixel activation scales of csrc/synthesis_x3.hip)."""
     x3 = plan.build_x3(x2)
-    assert len(x3["segments"]) == 1
-    seg, NT, HdP = x3["segments"][0], x3["NT"], x3["HdP"]
-    desc, tab = seg["desc"], seg["tables"].double()
-    stream = seg["stream"]
+    NT, HdP = x3["NT"], x3["HdP"]
+    desc, tab = x3["desc"], x3["tables"].double()
+    stream = x3["stream"]
     G, cst, ab = plan.x3_forward_tables(fmap_lowres.float(), fixed_style.float(), x2)
 
     def decode(stream_, stage0, KS, NT_):
@@ -136,14 +135,14 @@ def emulate(plan, fmap_lowres, fixed_style, Hr, Wr, H, W, x2=False):
                 # ToRGB head table of a skip block (round 5): the 8 lanes (rows 0-3, both halves) of a one-tile x2 stream of
                 # M_j = V_j W1_j -- scattered back into a full tile and decoded like any other x2 matrix; rows 0-2 are r, g, b
                 heads += 1
-                t8 = seg["tables"][d.b_conv: d.b_conv + 2 * NT * 64].contiguous().view(torch.int16).view(2 * NT, 2, 8, 8)
+                t8 = x3["tables"][d.b_conv: d.b_conv + 2 * NT * 64].contiguous().view(torch.int16).view(2 * NT, 2, 8, 8)
                 full = torch.zeros(2 * NT, 1, 2, 64, 8, dtype=torch.int16)
                 full[:, 0][:, :, [0, 1, 2, 3, 32, 33, 34, 35]] = t8
                 rgb = rgb + mm(y, decode_x2(full.flatten(), 0, 2 * NT, 1, dense=False))[..., :3]
         if bk.to_rgb:
             wr = torch.stack([vec(bk.w_rgb), vec(bk.w_rgb + HdP), vec(bk.w_rgb + 2 * HdP)])          # [3, HdP]
             rgb = rgb + x @ wr.t() + vec(bk.w_rgb + 3 * HdP, 3)
-    assert stage == seg["stages"]
+    assert stage == x3["stages"]
     if x2:      # the constant-style blocks in front of the first skip block (one in the shipped layouts): both convolutions in the x3 format
         n_mid = sum(2 for k in range(desc.n_blocks) if not desc.block[k].skip and not desc.block[k].spade[0].pixel_style
                     and not any(desc.block[q].skip for q in range(k)))
@@ -216,9 +215,10 @@ def test_head_tables_that_do_not_fit_the_lds_leave_the_plan_on_x2_with_the_ridin
         torch.manual_seed(0)
         sd = {k: v.detach().clone() for k, v in gens.Map3DGenerator(**meta).eval().state_dict().items()}
         plan = sp.SynthesisPlan(sd, "synthesis_network", "synthesis_input", n_blocks, (0, 1, 2), "mixed", torch.device("cpu"))
-        seg = plan.build_x3(True)["segments"][0]
+        seg = plan.build_x3(True)
         heads = any(seg["desc"].block[j].spade[1].b_conv >= 0 for j in range(seg["desc"].n_blocks))
-        assert heads == want_heads and plan.X2_HEADS == want_heads
+        assert heads == want_heads and seg["heads"] == want_heads
+        assert plan.X2_HEADS is True          # the request stays as it was: the planner's decision lives in the plan
         assert plan._x3_fits(True)
         assert lib.h3d_synthesis_x3_lds_bytes(seg["tables"].numel(), len(plan.const_ids), len(plan.pixel_ids), 256, 3 if heads else 1) <= 160 * 1024
         if not heads:          # every block that feeds ToRGB kept its own table

@@ -39,9 +39,8 @@ def contraction_names(desc):
 
 def emulate_subset(plan, G_rays, taps, wts, ii, jj, fixed_style, fmap_rays, x2_set):
     """x2_set: set of contraction indices evaluated in the x2 arithmetic (the rest exact) -> rgb [P, 3] float64."""
-    x3e, x3a = plan.build_x3(False), plan.build_x3(True)
-    seg_e, seg_a = x3e["segments"][0], x3a["segments"][0]
-    NT, HdP = x3a["NT"], x3a["HdP"]
+    seg_e, seg_a = plan.build_x3(False), plan.build_x3(True)
+    NT, HdP = seg_a["NT"], seg_a["HdP"]
     desc, tab = seg_a["desc"], seg_a["tables"].double()
     _, cst, ab = plan.x3_forward_tables(fmap_rays.float(), fixed_style.float(), True)
     vec = lambda off, n=HdP: tab[off: off + n]
@@ -129,7 +128,7 @@ def main():
     ii = torch.linspace(-1, 1, H, dtype=torch.float64)[Y]
     jj = torch.linspace(-1, 1, W, dtype=torch.float64)[X]
     style = ref["styles"].reshape(1, -1)
-    names = contraction_names(plan.build_x3(True)["segments"][0]["desc"])
+    names = contraction_names(plan.build_x3(True)["desc"])
     n = len(names)
     run = lambda s: emulate_subset(plan, G_rays, ref["taps"], wts, ii, jj, style, fm, s)
     exact = run(set())
