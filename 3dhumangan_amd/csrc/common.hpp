@@ -37,6 +37,14 @@ __host__ __device__ inline bool aligned16(const void* p) { return (reinterpret_c
 // Number of CUs of the current device (cached per device; falls back to the MI355X value).
 int compute_units();
 
+// Workgroups per batch item of a persistent grid [this, B]: about `per_cu` workgroups per CU in total walk the `groups` work items
+// of every batch item, so that the tables are staged once per many items while the tail of the launch stays short.
+inline int64_t persistent_wgs(int64_t groups, int B, int per_cu) {
+    const int64_t want = ((int64_t)per_cu * compute_units() + B - 1) / B;
+    const int64_t n = groups < want ? groups : want;
+    return n < 1 ? 1 : n;
+}
+
 // Function attributes are per device: raise the dynamic-LDS limit of `kernel` to the full 160 KB once per
 // (expansion site = kernel instantiation, device).  Idempotent, so a race between two host threads is harmless.
 #define H3D_ALLOW_MAX_LDS(kernel)                                                                         \

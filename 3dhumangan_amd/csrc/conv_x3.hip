@@ -454,9 +454,8 @@ extern "C" int h3d_conv_x3_ex(int mode, const void* x, const void* stream, const
 // The loop of a launch: tiling (NT_ = 0: the default blocking), whether it runs two workgroups per CU, iterations of the tap x chunk loop
 static int conv_plan(int Cin, int Cout, int k, int NT_, int* til, bool& occ2) {
     if (tiling_nt(Cin, Cout, NT_, til)) return -1;
-    // 1x1: two workgroups per CU on 4-k-step chunks (the stream's layout does not depend on the chunking); H3D_CONV_OCC=1: A/B knob
-    static const bool occ2_ok = [] { const char* e = getenv("H3D_CONV_OCC"); return !(e && e[0] == '1'); }();
-    occ2 = occ2_ok && k == 1;
+    // 1x1: two workgroups per CU on 4-k-step chunks (the stream's layout does not depend on the chunking)
+    occ2 = k == 1;
     if (occ2 && til[2] == 8) { til[2] = 4; til[3] *= 2; }
     return k * k * til[3];
 }
@@ -469,8 +468,7 @@ extern "C" int h3d_conv_x3_slices(int Cin, int Cout, int k, int64_t P, int NT) {
     int til[4];
     bool occ2;
     const int n_iter = conv_plan(Cin, Cout, k, NT, til, occ2);
-    static const bool split = [] { const char* e = getenv("H3D_CONV_SPLITK"); return !(e && e[0] == '0'); }();       // A/B knob
-    if (n_iter < 16 || !split) return 1;          // a short loop gains less than the second launch costs (1x1, 512 channels: 18 -> 24 us)
+    if (n_iter < 16) return 1;          // a short loop gains less than the second launch costs (1x1, 512 channels: 18 -> 24 us)
     const int64_t wgs = ((P + 127) / 128) * til[1];
     if (wgs >= 160) return 1;
     int s = (int)((256 + wgs - 1) / wgs);

@@ -37,7 +37,6 @@
 #include <string.h>
 #include <math.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include <algorithm>
 #include <type_traits>
 
@@ -807,14 +806,7 @@ int launch_one(Args A, int B, int64_t groups, hipStream_t st) {
     H3D_ALLOW_MAX_LDS((field_x3_kernel<NT, FUSED, X2, GEOIN>));
     A.n_groups = (int)groups;
     // about four persistent workgroups per CU in total (one resident per CU: registers): tables once per many unit groups, short tail
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-    }
-    static const int per_cu = getenv("H3D_FIELD_WG_PER_CU") ? atoi(getenv("H3D_FIELD_WG_PER_CU")) : 4;      // 0: one unit group per workgroup
-    int64_t per_sample = per_cu <= 0 ? groups : std::max<int64_t>(1, std::min<int64_t>(groups, ((int64_t)per_cu * cus + B - 1) / B));
+    int64_t per_sample = h3d::persistent_wgs(groups, B, 4);
     // refinement launch: a handful of listed units per batch item (workgroups beyond the list leave at once)
     if (A.ref_mode == 2) per_sample = std::max<int64_t>(1, std::min<int64_t>((A.ref_cap + 3) / 4, 8));
     h3d::pre_launch();

@@ -18,7 +18,6 @@
 #include <algorithm>
 #include <math.h>
 #include <stdio.h>
-#include <stdlib.h>
 
 using namespace h3d;
 
@@ -628,14 +627,7 @@ int launch_one(Args A, int B, int64_t groups, hipStream_t st) {
     H3D_ALLOW_MAX_LDS((field_x3t_kernel<NTF, NX, FUSED, P>));
     A.n_groups = (int)groups;
     // about eight persistent workgroups per CU in total (one resident per CU: LDS): tables once per many groups, short tail
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-    }
-    static const int per_cu = getenv("H3D_FIELD_X3T_WG_PER_CU") ? atoi(getenv("H3D_FIELD_X3T_WG_PER_CU")) : 8;      // 0: one group per workgroup
-    const int64_t per_sample = per_cu <= 0 ? groups : std::max<int64_t>(1, std::min<int64_t>(groups, ((int64_t)per_cu * cus + B - 1) / B));
+    const int64_t per_sample = h3d::persistent_wgs(groups, B, 8);
     h3d::pre_launch();
     hipLaunchKernelGGL((field_x3t_kernel<NTF, NX, FUSED, P>), dim3((unsigned)per_sample, (unsigned)B), dim3(256), lds_bytes(A.L), st, A);
     return h3d::launch_status(FUSED ? "h3d_render_fused_x3t" : "h3d_neural_field_x3t");

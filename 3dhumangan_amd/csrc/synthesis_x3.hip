@@ -21,7 +21,6 @@
 // bf16 products (12 small MFMAs per SPADE).
 #include "x3_common.hpp"
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 using namespace h3d;
@@ -677,17 +676,8 @@ int launch_variant(Args A, int B, int64_t groups, hipStream_t st) {
     groups = A.n_walk;
     // persistent workgroups (one per CU at a time: registers and LDS): about four per CU in total, so that the tables are staged
     // once per ~n_tiles * B / (4 CUs) tiles while the tail of the launch stays short
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-    }
-    static const int per_cu = getenv("H3D_SYNTH_WG_PER_CU") ? atoi(getenv("H3D_SYNTH_WG_PER_CU")) : 4;      // 0: one tile per workgroup
     // (a fallback launch -- run_if -- usually redoes ONE sample of the batch: that sample's workgroups must fill the chip by themselves)
-    const int64_t per_sample = per_cu <= 0 ? groups
-                             : A.run_if ? std::min<int64_t>(groups, cus)
-                             : std::max<int64_t>(1, std::min<int64_t>(groups, ((int64_t)per_cu * cus + B - 1) / B));
+    const int64_t per_sample = A.run_if ? std::min<int64_t>(groups, h3d::compute_units()) : h3d::persistent_wgs(groups, B, 4);
     h3d::pre_launch();
     hipLaunchKernelGGL((synthesis_x3_kernel<NT, DEPTH, X2, HEADS, MIDX3>), dim3((unsigned)per_sample, (unsigned)B), dim3(256),
                        lds_bytes(A, NT, DEPTH + (X2 ? 1 : 0)), st, A);

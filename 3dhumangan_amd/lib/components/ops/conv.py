@@ -54,8 +54,6 @@ _stream_cache = {}
 # autocast rounds it: one matrix product per weight, half the weight stream (h3d_conv_x3_f16x1); 2 = f16 hi + lo (the weight to
 # max(2^-22 |W|, 2^-25): more precise than what it is compared with, twice the matrix work) -- the opt-in tier.
 AMP_WEIGHT_PLANES = int(os.environ.get("H3D_AMP_WEIGHT_PLANES", "1"))
-FUSED_PAD = os.environ.get("H3D_CONV_PAD", "fused") != "torch"             # channel padding on h3d_pad_channels_cl (round 6)
-FUSED_REDUCE = os.environ.get("H3D_WGRAD_REDUCE", "fused") != "torch"      # the slices' sum on h3d_wgrad_reduce (round 6)
 
 
 def pack_stream(w, transposed=False, half=False, owner=None, planes=2, nt=0):
@@ -102,9 +100,6 @@ def pack_stream_torch(w):
     return torch.stack([hi, lo], dim=5).contiguous().view(torch.int16)    # ob, tap, chunk, ks, nt, (hi|lo), h, j, e
 
 
-_copied = {}          # H3D_CONV_DEBUG=1: (shape, strides) of tensors that had to be copied to channels-last, with counts
-
-
 def _rows(x):
     """x [B, C, H, W] -> (tensor whose memory is pixel-major rows of C floats, row stride in floats).  Channels-last tensors and
     channel slices of channels-last tensors (what the backward of a skip concatenation hands out) are taken as they are;
@@ -116,9 +111,6 @@ def _rows(x):
     gran = 4 if x.dtype == torch.float32 else 8           # 16-byte accesses: 4 floats or 8 halves
     if (sc == 1 and ld >= C and ld % gran == 0 and sh == W * ld and (sb == H * W * ld or B == 1) and x.data_ptr() % 16 == 0):
         return x, ld
-    if os.environ.get("H3D_CONV_DEBUG"):
-        key = (tuple(x.shape), tuple(x.stride()))
-        _copied[key] = _copied.get(key, 0) + 1
     return _lib.aligned16(x.contiguous(memory_format=torch.channels_last)), C
 
 
@@ -186,9 +178,6 @@ def reduce_slices(partial, colsum, taps, slices, co, ci, shape):
     """partial [taps, slices, co, ci] (, colsum [slices, co]) -> dw `shape` = [co, ci (, k, k)] (, db [co]): the slices' sum, the
     layout change and the bias gradient's sum in ONE launch (h3d_wgrad_reduce; torch: a reduction, a permuted copy and a second
     reduction -- three launches per weight gradient)."""
-    if not FUSED_REDUCE:                  # H3D_WGRAD_REDUCE=torch: the round-5 tensor operations (A/B switch)
-        dw = partial.view(taps, slices, co, ci).sum(dim=1).permute(1, 2, 0).contiguous().view(shape)
-        return dw if colsum is None else (dw, colsum.sum(dim=0))
     dw = torch.empty(shape, device=partial.device, dtype=torch.float32)
     db = None if colsum is None else torch.empty((co,), device=partial.device, dtype=torch.float32)
     rc = _lib.load().h3d_wgrad_reduce(_lib.ptr(partial), _lib.ptr(colsum), _lib.ptr(dw), _lib.ptr(db), taps, slices, co, ci,
@@ -306,10 +295,6 @@ def _pad_channels(x, cop):
     _lib.need_cuda(x)
     x = x.detach()
     B, C, H, W = x.shape
-    if not FUSED_PAD:                      # H3D_CONV_PAD=torch: the round-5 tensor operations (A/B switch)
-        x = x.contiguous(memory_format=torch.channels_last)
-        out = torch.cat([x, x.new_zeros((B, cop - C, H, W)).contiguous(memory_format=torch.channels_last)], dim=1)
-        return out.contiguous(memory_format=torch.channels_last)
     sb, sc, sh, sw = x.stride()
     if H > 1 and W > 1 and sh != W * sw:   # rows that do not follow each other: not a pixel-strided layout
         x = x.contiguous(memory_format=torch.channels_last)

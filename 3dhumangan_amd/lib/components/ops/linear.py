@@ -3,10 +3,13 @@
 
 Forward / data gradient ([M, C] x [C, C'] with M ~ 0.5 M rows): hipBLASLt runs them in fp32 at 131 TFLOP/s (83 % of the fp32 matrix
 peak); h3d_conv_x3 evaluates the same contraction with split bf16 operands (three 16-bit products, ~2e-5) at ~230 TFLOP/s, bias
-fused, when both widths are multiples of 64 (`H3D_LINEAR=library` keeps the library GEMM).  The WEIGHT gradient dW = dY^T X
-contracts over the M rows and produces a tiny output -- the library runs it at ~50 TFLOP/s, h3d_wgrad_x3 streams both operands once
-(HBM-bound) and returns the bias gradient from the same pass.  Used by lib/generators/differentiable.py for every layer with enough
-rows; anything else (few rows, half-precision autocast inputs, odd widths, CPU tensors) is F.linear."""
+fused, when both widths are multiples of 64.  The WEIGHT gradient dW = dY^T X contracts over the M rows and produces a tiny output
+-- the library runs it at ~50 TFLOP/s, h3d_wgrad_x3 streams both operands once (HBM-bound) and returns the bias gradient from the
+same pass.  Used by lib/generators/differentiable.py for every layer with enough rows; anything else (few rows, half-precision
+autocast inputs, odd widths, CPU tensors) is F.linear.  Which of them a call takes is decided in one place, _route
+(tests/test_linear_dispatch_cpu.py pins it)."""
+import collections
+import functools
 import os
 import weakref
 
@@ -15,13 +18,9 @@ import torch.nn.functional as F
 
 from .... import _lib
 
-MIN_ROWS = int(os.environ.get("H3D_WGRAD_MIN_ROWS", 16384))      # below this the library GEMM is as good
-SMALL_ROWS = int(os.environ.get("H3D_AMP_FP32_ROWS", 64))            # AMP: layers with fewer rows than this run in fp32 (0: autocast decides)
+MIN_ROWS = 16384          # below this the library GEMM is as good
+SMALL_ROWS = 64           # AMP: layers with fewer rows than this run in fp32
 ENABLED = os.environ.get("H3D_WGRAD", "x3") == "x3"
-NATIVE_GEMM = os.environ.get("H3D_LINEAR", "x3") == "x3"
-FUSED_ADD = os.environ.get("H3D_LINEAR_ADD", "fused") != "torch"          # residual addend in the GEMM epilogue (round 6; A/B switch)
-AMP_NATIVE_GEMM = os.environ.get("H3D_AMP_LINEAR", "library") == "x3"      # AMP forward / data gradient: library f16 GEMM by default
-PAD_ODD_WIDTH = os.environ.get("H3D_LINEAR_PAD", "1") != "0"                 # odd input widths padded for the weight-gradient kernel (round 6; A/B switch)
 FUSED_MOMENTS = os.environ.get("H3D_FUSED_MOMENTS", "1") != "0"             # BatchNorm moments from the GEMM's accumulators (round 6; A/B switch)
 # autocast dense layers WITH a residual addend on the own f16 GEMM (addend in the epilogue): opt-in -- measured slower in the iteration
 # (106.0 -> 110.4 ms, profiles/r6_ab_amp_linear_add_not_kept.txt): in situ the own GEMM loses more to the library's than the sum's pass costs
@@ -72,9 +71,11 @@ def gemm_x3(x2, w, bias=None, transposed=False, add=None, moments=False):
     return y.permute(0, 2, 3, 1).reshape(x2.shape[0], -1)
 
 
+@functools.lru_cache(maxsize=None)
 def _native_ok(Co, Ci):
+    """h3d_conv_x3 takes a Ci -> Co layer and its transpose (a function of the widths alone; asked on every call of linear())."""
     from . import conv
-    return NATIVE_GEMM and Co % 64 == 0 and Ci % 64 == 0 and conv.tiling(Ci, Co) is not None and conv.tiling(Co, Ci) is not None
+    return Co % 64 == 0 and Ci % 64 == 0 and conv.tiling(Ci, Co) is not None and conv.tiling(Co, Ci) is not None
 
 
 def wgrad_x3(dy, x, with_bias=False):
@@ -133,6 +134,23 @@ def _rows(t):
     return _lib.aligned16(t2)          # a contiguous view at an odd storage offset is copied (.contiguous() would return it as is)
 
 
+def _weight_grad(dy2, x2, want_db):
+    """dy2 [M, Co], x2 [M, Ci] (both from _rows, fp32 or both f16) -> (dw [Co, Ci] fp32, db): the weight gradient on the kernel built
+    for its shape; db [Co] where that kernel's pass over dy yields the bias gradient as well (want_db), else None."""
+    Co, Ci = dy2.shape[1], x2.shape[1]
+    if Co <= 4:
+        dw = wgrad_narrow(x2, dy2, narrow_sum=want_db)           # [Co, Ci] (, column sums of dy: the bias gradient)
+        return dw if want_db else (dw, None)
+    if Ci <= 3 and want_db:
+        dw, db = wgrad_narrow(dy2, x2, wide_sum=True)            # [Ci, Co], column sums of dy
+        return dw.t(), db
+    if Ci <= 4:
+        return wgrad_narrow(dy2, x2).t(), None                   # [Ci, Co] -> [Co, Ci]
+    if want_db:
+        return wgrad_x3(dy2, x2, with_bias=True)                 # the bias gradient rides along: no second pass over dy
+    return wgrad_x3(dy2, x2), None
+
+
 class _LinearX3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, add=None, moments=False):
@@ -156,35 +174,21 @@ class _LinearX3(torch.autograd.Function):
         x, w = ctx.saved_tensors
         dx = dw = db = None
         dy2 = _rows(dy)
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[0]:
             dx = gemm_x3(dy2, w, transposed=True).view(*dy.shape[:-1], w.shape[1]) if _native_ok(*w.shape) else dy @ w
         if ctx.needs_input_grad[1]:
-            Co, Ci = w.shape
-            want_db = ctx.has_bias and ctx.needs_input_grad[2]
-            if Co <= 4:
-                dw = wgrad_narrow(_rows(x), dy2, narrow_sum=want_db)   # [Co, Ci] (, column sums of dy: the bias gradient)
-                if want_db:
-                    dw, db = dw
-            elif Ci <= 3 and want_db:
-                dw, db = wgrad_narrow(dy2, _rows(x), wide_sum=True)  # [Ci, Co], column sums of dy
-                dw = dw.t()
-            elif Ci <= 4:
-                dw = wgrad_narrow(dy2, _rows(x)).t()                 # [Ci, Co] -> [Co, Ci]
-            elif ctx.has_bias and ctx.needs_input_grad[2]:
-                dw, db = wgrad_x3(dy2, _rows(x), with_bias=True)      # the bias gradient rides along: no second pass over dy
-            else:
-                dw = wgrad_x3(dy2, _rows(x))
-        if db is None and ctx.has_bias and ctx.needs_input_grad[2]:
+            dw, db = _weight_grad(dy2, _rows(x), want_db)
+        if db is None and want_db:
             db = dy2.sum(dim=0)
         return dx, dw, db, (dy if ctx.needs_input_grad[3] else None), None    # the addend's gradient is the output's
 
 
 class _LinearAmp(torch.autograd.Function):
     """The dense layer under float16 autocast (AMP tier, round 4; reference: nn.Linear / 1x1 convs inside torch.cuda.amp.autocast):
-    forward and data gradient are the library's f16 GEMMs on f16 activations (HBM-bound there: 126 us for 0.5 M x 256 x 256), or
-    h3d_conv_x3_f16 with H3D_AMP_LINEAR=x3; the weight gradient (tall-skinny TN, the shape the library is slow at: 4 ms for a
-    3 x 256 result) is h3d_wgrad_x3 / h3d_wgrad_narrow on the f16 operands as they are -- fp32 result, no casts; the weight
-    stays fp32."""
+    forward and data gradient are the library's f16 GEMMs on f16 activations (HBM-bound there: 126 us for 0.5 M x 256 x 256); the
+    weight gradient (tall-skinny TN, the shape the library is slow at: 4 ms for a 3 x 256 result) is h3d_wgrad_x3 / h3d_wgrad_narrow
+    on the f16 operands as they are -- fp32 result, no casts; the weight stays fp32."""
 
     @staticmethod
     def forward(ctx, x, w, b, add=None, moments=False):
@@ -199,9 +203,9 @@ class _LinearAmp(torch.autograd.Function):
             y, partial = gemm_x3(_rows(xh), w, b, add=a2, moments=True)
             ctx.mark_non_differentiable(partial)
             return y.view(*x.shape[:-1], w.shape[0]), partial
-        if (AMP_NATIVE_GEMM or (add is not None and AMP_ADD_NATIVE)) and _native_ok(*w.shape):
-            # opt-in paths: the own f16 GEMM, the addend (if any) in its epilogue -- added in fp32, one rounding
-            y = gemm_x3(_rows(xh), w, b, add=None if add is None else _rows(add.detach().half()))
+        if add is not None and AMP_ADD_NATIVE and _native_ok(*w.shape):
+            # opt-in path: the own f16 GEMM, the addend in its epilogue -- added in fp32, one rounding
+            y = gemm_x3(_rows(xh), w, b, add=_rows(add.detach().half()))
             return y.view(*x.shape[:-1], w.shape[0])
         y = F.linear(xh, _half_cached(w), _half_cached(b))
         return y if add is None else y + add
@@ -212,31 +216,83 @@ class _LinearAmp(torch.autograd.Function):
         xh, w = ctx.saved_tensors
         dyh = dy.half()
         dx = dw = db = None
-        dy2, x2 = _rows(dyh), _rows(xh)
+        dy2 = _rows(dyh)
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[0]:
-            if AMP_NATIVE_GEMM and _native_ok(*w.shape):
-                dx = gemm_x3(dy2, w, transposed=True).view(*dy.shape[:-1], w.shape[1])
-            else:
-                dx = dyh @ _half_cached(w)
+            dx = dyh @ _half_cached(w)
         if ctx.needs_input_grad[1]:
-            Co, Ci = w.shape
-            want_db = ctx.has_bias and ctx.needs_input_grad[2]
-            if Co <= 4:
-                dw = wgrad_narrow(x2, dy2, narrow_sum=want_db)       # [Co, Ci] (, column sums of dy: the bias gradient)
-                if want_db:
-                    dw, db = dw
-            elif Ci <= 3 and want_db:
-                dw, db = wgrad_narrow(dy2, x2, wide_sum=True)        # [Ci, Co], column sums of dy
-                dw = dw.t()
-            elif Ci <= 4:
-                dw = wgrad_narrow(dy2, x2).t()                       # [Ci, Co] -> [Co, Ci]
-            elif ctx.has_bias and ctx.needs_input_grad[2]:
-                dw, db = wgrad_x3(dy2, x2, with_bias=True)
-            else:
-                dw = wgrad_x3(dy2, x2)
-        if db is None and ctx.has_bias and ctx.needs_input_grad[2]:
+            dw, db = _weight_grad(dy2, _rows(xh), want_db)
+        if db is None and want_db:
             db = dy2.sum(dim=0, dtype=torch.float32)
         return dx, dw, db, (dy if ctx.needs_input_grad[3] else None), None
+
+
+# What linear() decides on.  amp: "off", "f16" or "other" (the autocast state); add_dt: None without an addend; native: the widths are
+# ones h3d_conv_x3 takes (_native_ok; asked for CUDA tensors only); add_fits: the addend has the output's shape (no broadcast).
+_Call = collections.namedtuple("_Call", "cuda x_dt w_dt add_dt amp grad x_req w_req add_req rows Co Ci native add_fits")
+
+
+def _facts(x, w, add):
+    Co, Ci = w.shape
+    amp = "off"
+    if torch.is_autocast_enabled():
+        amp = "f16" if torch.get_autocast_dtype("cuda") == torch.float16 else "other"
+    return _Call(cuda=x.is_cuda, x_dt=x.dtype, w_dt=w.dtype, add_dt=None if add is None else add.dtype, amp=amp,
+                 grad=torch.is_grad_enabled(), x_req=x.requires_grad, w_req=w.requires_grad,
+                 add_req=add is not None and add.requires_grad, rows=x.numel() // max(Ci, 1), Co=Co, Ci=Ci,
+                 native=x.is_cuda and _native_ok(Co, Ci), add_fits=add is not None and add.shape == x.shape[:-1] + (Co,))
+
+
+def _route(c, moments=False):
+    """The kernel for a call with the facts c -- one of
+        "x3"        _LinearX3: fp32, the weight gradient on h3d_wgrad_x3 / h3d_wgrad_narrow, forward and data gradient on h3d_conv_x3
+                    where the widths allow, addend and moments in its epilogue;
+        "amp"       _LinearAmp: the same under float16 autocast, on f16 operands;
+        "gemm"      h3d_conv_x3 on its own: fp32 with nothing to record (the D step's generator forward);
+        "few_rows"  F.linear in fp32 outside the float16 autocast;
+        "library"   F.linear;
+    or a reduction of the request, dispatched again:
+        "pad"              the input width zero-padded to a multiple of 8;
+        "add_after"        linear(x, w, b) + add;
+        "without_moments"  (linear(x, w, b, add), None)."""
+    fp32 = c.cuda and c.amp == "off" and c.x_dt == torch.float32 and c.w_dt == torch.float32
+    amp16 = c.cuda and c.amp == "f16" and c.w_dt == torch.float32          # autocast casts the input, whatever its type
+    big = c.rows >= MIN_ROWS
+    trains = ENABLED and c.grad and c.w_req                              # a weight gradient will be asked for
+    recorded = c.grad and (c.x_req or c.w_req or c.add_req)                # autograd records the call: a bare kernel would cut the graph
+    has_add = c.add_dt is not None
+    if moments or has_add:
+        # epilogue extras: only the native GEMM has them, for an addend of the output's shape and type
+        fused = big and c.native and (c.add_fits or not has_add) and (FUSED_MOMENTS or not moments)
+        if fused and amp16 and ENABLED and (AMP_FUSED_MOMENTS if moments else AMP_ADD_NATIVE):
+            return "amp"                                                   # opt-in: the own f16 GEMM (the addend is cast to f16)
+        if fused and fp32 and c.add_dt in (None, torch.float32):
+            if trains:
+                return "x3"
+            if not recorded:
+                return "gemm"
+        return "without_moments" if moments else "add_after"
+    wide = c.Co >= 32 and c.Ci >= 32
+    narrow = (c.Co <= 4 and c.Ci >= 32) or (c.Ci <= 4 and c.Co >= 32)      # h3d_wgrad_narrow: heads, ToRGB, coordinates
+    if (trains and big and c.cuda and c.w_dt == torch.float32 and not c.x_req and (c.x_dt == torch.float32 or c.amp != "off")
+            and c.Co % 8 == 0 and c.Co >= 32 and c.Ci > 4 and c.Ci % 8):
+        # an input width the weight-gradient kernel does not take (the field's 31 geometry features, map3d_layers / smpl.py:210-249):
+        # one zero column more and the layer's weight gradient leaves the library's tall-skinny TN GEMM (0.99 ms at 0.59 M rows x 31 ->
+        # 256) for h3d_wgrad_x3 (round 6).  The input needs no gradient (it is data), the weight's comes back through the pad.
+        return "pad"
+    if trains and big and amp16 and (narrow or (wide and c.Co % 8 == 0 and c.Ci % 8 == 0)):
+        return "amp"
+    if trains and big and fp32 and (narrow or (wide and c.Co % 4 == 0 and c.Ci % 4 == 0)):
+        return "x3"
+    if fp32 and big and c.native and not recorded:
+        return "gemm"
+    if c.cuda and c.amp == "f16" and c.rows < SMALL_ROWS:
+        # a handful of rows (per-sample style vectors: the constant SPADEs' modulation, the shared layers' offsets) under float16
+        # autocast: computed in fp32 (round 6).  Autocast would convert both parameters on every call -- the weight handed in is a
+        # view of the parameter, which its cache never holds -- and their gradients back: 4 launches per layer and pass, ~350 per
+        # config-4 iteration, for products of 4 x 128 x 256.
+        return "few_rows"
+    return "library"
 
 
 def linear(x, w, b=None, add=None, moments=False):
@@ -245,61 +301,25 @@ def linear(x, w, b=None, add=None, moments=False):
     moments=True: -> (y, partial): partial [rows, 2, Co] fp32 holds per-workgroup column sums of y and y^2 taken from the GEMM's
     accumulators (h3d_conv_x3_moments; spade_norm_act(.., moments=partial) then skips its own pass over y), or None where the call
     does not run on the native fp32 GEMM (the SPADE computes them itself)."""
-    if moments:
-        Co, Ci = w.shape
-        rows = x.numel() // max(Ci, 1)
-        if (AMP_FUSED_MOMENTS and FUSED_MOMENTS and ENABLED and x.is_cuda and torch.is_autocast_enabled()
-                and torch.get_autocast_dtype("cuda") == torch.float16 and w.dtype == torch.float32 and rows >= MIN_ROWS and _native_ok(Co, Ci) and Co >= 32 and Ci >= 32
-                and (add is None or add.shape == x.shape[:-1] + (Co,))):
-            return _LinearAmp.apply(x, w, b, add, True)
-        ok = (FUSED_MOMENTS and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and not torch.is_autocast_enabled()
-              and rows >= MIN_ROWS and _native_ok(Co, Ci) and (add is None or (FUSED_ADD and add.dtype == torch.float32
-                                                                              and add.shape == x.shape[:-1] + (Co,))))
-        if ok and ENABLED and torch.is_grad_enabled() and w.requires_grad and Co >= 32 and Ci >= 32:
-            return _LinearX3.apply(x, w, b, add, True)
-        if ok and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (add is not None and add.requires_grad))):
-            y, partial = gemm_x3(_rows(x), w, b, add=None if add is None else _rows(add), moments=True)
-            return y.view(*x.shape[:-1], Co), partial
+    c = _facts(x, w, add)
+    route = _route(c, moments)
+    if route == "without_moments":
         return linear(x, w, b, add), None
-    Co, Ci = w.shape
-    rows = x.numel() // max(Ci, 1)
-    if (PAD_ODD_WIDTH and ENABLED and add is None and x.is_cuda and w.dtype == torch.float32 and torch.is_grad_enabled() and w.requires_grad
-            and not x.requires_grad and rows >= MIN_ROWS and Co % 8 == 0 and Co >= 32 and Ci > 4 and Ci % 8
-            and (x.dtype == torch.float32 or torch.is_autocast_enabled())):
-        # an input width the weight-gradient kernel does not take (the field's 31 geometry features, map3d_layers / smpl.py:210-249):
-        # one zero column more and the layer's weight gradient leaves the library's tall-skinny TN GEMM (0.99 ms at 0.59 M rows x 31 ->
-        # 256) for h3d_wgrad_x3 (round 6).  The input needs no gradient (it is data), the weight's comes back through the pad.
-        pad = 8 - Ci % 8
-        return linear(F.pad(x, (0, pad)), F.pad(w, (0, pad)), b)
-    if (add is not None and AMP_ADD_NATIVE and FUSED_ADD and ENABLED and x.is_cuda and torch.is_autocast_enabled()
-            and torch.get_autocast_dtype("cuda") == torch.float16 and w.dtype == torch.float32 and rows >= MIN_ROWS and _native_ok(Co, Ci)
-            and Co >= 32 and Ci >= 32 and add.shape == x.shape[:-1] + (Co,)):
-        return _LinearAmp.apply(x, w, b, add, False)
-    if add is not None:
-        fp32 = (FUSED_ADD and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and add.dtype == torch.float32
-                and not torch.is_autocast_enabled() and rows >= MIN_ROWS and _native_ok(Co, Ci) and add.shape == x.shape[:-1] + (Co,))
-        if fp32 and ENABLED and torch.is_grad_enabled() and w.requires_grad and Co >= 32 and Ci >= 32:
-            return _LinearX3.apply(x, w, b, add)
-        if fp32 and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or add.requires_grad)):
-            return gemm_x3(_rows(x), w, b, add=_rows(add)).view(*x.shape[:-1], Co)
+    if route == "add_after":
         return linear(x, w, b) + add
-    if (ENABLED and x.is_cuda and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16
-            and torch.is_grad_enabled() and w.requires_grad and w.dtype == torch.float32 and rows >= MIN_ROWS
-            and ((Co % 8 == 0 and Ci % 8 == 0 and Co >= 32 and Ci >= 32) or (Co <= 4 and Ci >= 32) or (Ci <= 4 and Co >= 32))):
-        return _LinearAmp.apply(x, w, b, None, False)
-    if (ENABLED and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and torch.is_grad_enabled()
-            and w.requires_grad and not torch.is_autocast_enabled() and rows >= MIN_ROWS
-            and ((Co % 4 == 0 and Ci % 4 == 0 and Co >= 32 and Ci >= 32)           # h3d_wgrad_x3
-                 or (Co <= 4 and Ci >= 32) or (Ci <= 4 and Co >= 32))):             # h3d_wgrad_narrow (heads, ToRGB, coordinates)
-        return _LinearX3.apply(x, w, b, None)
-    if (x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and not torch.is_autocast_enabled() and rows >= MIN_ROWS
-            and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad)) and _native_ok(Co, Ci)):
-        return gemm_x3(_rows(x), w, b).view(*x.shape[:-1], Co)          # nothing to record (the D step's generator forward)
-    if x.is_cuda and rows < SMALL_ROWS and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16:
-        # a handful of rows (per-sample style vectors: the constant SPADEs' modulation, the shared layers' offsets) under float16
-        # autocast: computed in fp32 (round 6).  Autocast would convert both parameters on every call -- the weight handed in is a
-        # view of the parameter, which its cache never holds -- and their gradients back: 4 launches per layer and pass, ~350 per
-        # config-4 iteration, for products of 4 x 128 x 256.
+    if route == "pad":
+        pad = 8 - c.Ci % 8
+        return linear(F.pad(x, (0, pad)), F.pad(w, (0, pad)), b)
+    if route == "x3":
+        return _LinearX3.apply(x, w, b, add, moments)
+    if route == "amp":
+        return _LinearAmp.apply(x, w, b, add, moments)
+    if route == "gemm":
+        y = gemm_x3(_rows(x), w, b, add=None if add is None else _rows(add), moments=moments)
+        if moments:
+            return y[0].view(*x.shape[:-1], c.Co), y[1]
+        return y.view(*x.shape[:-1], c.Co)
+    if route == "few_rows":
         with torch.autocast("cuda", enabled=False):
             return F.linear(x.float(), w.float(), None if b is None else b.float())
     return F.linear(x, w, b)

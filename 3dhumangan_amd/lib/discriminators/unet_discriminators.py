@@ -45,8 +45,8 @@ class Conv2d(nn.Conv2d):
         if hook is not None:
             # spectral normalisation (round 4): torch's forward pre-hook was taken off the module by _conv(); the same arithmetic
             # runs here -- on the fused kernels (ops/spectral.py) in the case the trainer is in, through torch's own
-            # SpectralNorm.compute_weight otherwise (eval mode, CPU, H3D_DISC_SN=torch)
-            if os.environ.get("H3D_DISC_SN", "hip") != "torch" and spectral_ops.supported(self, hook):
+            # SpectralNorm.compute_weight otherwise (eval mode, CPU)
+            if spectral_ops.supported(self, hook):
                 setattr(self, hook.name, spectral_ops.spectral_weight(self, hook))
             else:
                 hook(self, None)
@@ -118,9 +118,9 @@ class ResBlock(nn.Module):
             the sum (differs from the reference's two by fp32 rounding order, ~1e-7).
         The first block keeps the reference's order (pool BEFORE its 1x1 convolution: already the cheap one).
         The resampling / activation glue runs on two fused kernels (ops/pool_up.py: up(lrelu(x)) in one pass, up(s) + d,
-        avgpool(s + d) -- each the other's adjoint, so the R1 double backward stays on them); `H3D_DISC_GLUE=torch` keeps
+        avgpool(s + d) -- each the other's adjoint, so the R1 double backward stays on them); CPU tensors and odd sizes keep
         F.leaky_relu / F.interpolate / F.avg_pool2d."""
-        fused = x.is_cuda and os.environ.get("H3D_DISC_GLUE", "hip") != "torch" and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
+        fused = x.is_cuda and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
         if self.first and self.up_or_down >= 0:
             fused = False       # the fused first-block glue IS the average pooling: a first block that does not go down keeps _resample
         d = x

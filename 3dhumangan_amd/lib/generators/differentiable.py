@@ -19,8 +19,6 @@ one is initialised -- the reference uses nn.SyncBatchNorm, lib/components/map3d_
 updates, and one spectral-norm power iteration per conv and call (torch.nn.utils.spectral_norm as used at
 lib/components/map3d_layers.py:205-206).
 """
-import os
-
 import torch
 import torch.nn.functional as F
 
@@ -29,10 +27,6 @@ from ..components.ops.linear import linear
 from ..components.ops.spade import spade_norm_act
 from ..components.ops.spectral import _SpectralWeight
 from ..components.resample import bilinear_resize_cl, bilinear_resize_relu_cl
-
-FUSED_SPECTRAL = os.environ.get("H3D_GEN_SN", "hip") != "torch"      # the generator's spectral norm on csrc/spectral_norm.hip (round 6)
-ALIAS_GRADS = os.environ.get("H3D_SPADE_ALIAS", "1") != "0"      # gradients of a skip block's input summed inside the SPADE backward kernel (round 6)
-
 
 # ------------------------------------------------------------------------------------------------ A5: the implicit function
 
@@ -72,7 +66,7 @@ def spectral_weight(conv, training, eps=1e-12):
 
 def _spectral_weight_fp32(conv, training, eps):
     w0, u, v = conv.weight_orig, conv.weight_u, conv.weight_v
-    if (training and FUSED_SPECTRAL and w0.is_cuda and w0.dtype == torch.float32 and u.dtype == torch.float32 and v.dtype == torch.float32
+    if (training and w0.is_cuda and w0.dtype == torch.float32 and u.dtype == torch.float32 and v.dtype == torch.float32
             and u.is_contiguous() and v.is_contiguous()):
         # round 6: the discriminator's fused kernels (ops/spectral.py: three launches forward, two backward) instead of ~16 + ~10
         # tensor operations per layer and pass -- 36 calls per config-4 iteration
@@ -97,9 +91,6 @@ def _coords(H, W, device, dtype):
     return torch.stack([ii, jj], dim=-1).reshape(H * W, 2)
 
 
-FUSED_RESIZE_RELU = os.environ.get("H3D_RESIZE_RELU", "fused") != "torch"      # ReLU + its mask inside the resize kernels (round 6; A/B switch)
-
-
 def _resize_channels_last(t, render_hw, gen_hw, relu=False):
     """Bilinear (align_corners=False) resize of a channels-last map [B, Hr*Wr, C] -> [B, H*W, C] without leaving the
     channels-last layout (F.interpolate on the NCHW *view* of the same memory)."""
@@ -107,7 +98,7 @@ def _resize_channels_last(t, render_hw, gen_hw, relu=False):
     if t.is_cuda and t.dtype in (torch.float32, torch.float16) and C % 4 == 0 and B * gen_hw[0] < 65536:
         # own kernels: the backward reads the gradient once, no atomics.  Under autocast too (F.interpolate's channels-last
         # kernels take 3.4 ms forward + 4.9 ms backward here, these 0.5 + 0.3 ms): computed in fp32, returned in the input's type
-        if relu and FUSED_RESIZE_RELU and t.dtype == torch.float32:
+        if relu and t.dtype == torch.float32:
             # fp32 only: under float16 autocast the mask would be the saved fp32 output (twice the bytes of the f16 ReLU's) and
             # the iteration gets 1.5 ms slower (profiles/r6_ab_resize_relu.txt)
             return bilinear_resize_relu_cl(t, render_hw, gen_hw)
@@ -183,7 +174,7 @@ def synthesis_forward(G, fmap_low, styles, render_hw, gen_hw, training, group=No
         # A skip block's input feeds its first SPADE, its residual connection and the previous block's ToRGB head.  When autograd
         # records, the last two read x through views handed out by the SPADE node, whose backward kernel adds their gradients into
         # dx as it writes it (h3d_spade_bwd_apply_acc) -- two accumulation passes over [B, P, C] less per block (round 6).
-        n_alias = (int(skip) + int(pending is not None)) if (ALIAS_GRADS and torch.is_grad_enabled() and x.requires_grad) else 0
+        n_alias = (int(skip) + int(pending is not None)) if (torch.is_grad_enabled() and x.requires_grad) else 0
         out = spade_norm_act(x, *modulation(name, "spade_0", idx), training, group, kernels=spade_kernels, aliases=n_alias,
                              moments=mom_x)
         h, views = (out[0], list(out[1:])) if n_alias else (out, [])

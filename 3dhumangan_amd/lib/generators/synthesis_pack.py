@@ -510,10 +510,10 @@ class SynthesisPlan:
                     ab_carry=ab_carry, heads=bool(merged))
 
     # Requests (the outcome is build_x3(True)["heads"]): ToRGB head tables in x2 plans
-    X2_HEADS = os.environ.get("H3D_SYNTH_HEADS", "1") != "0"
+    X2_HEADS = True
     # x2 plans: the base of the residual stream (the constant-style block in front of the first skip block) on three bf16 products
     # -- the per-contraction attribution's largest contributor (b3.conv1 4.8e-4, b3.conv0 2.3e-4 of an all-x2 7.9e-4)
-    X2_MID_X3 = os.environ.get("H3D_SYNTH_MID_X3", "1") != "0"
+    X2_MID_X3 = True
 
     def _torgb_heads(self, desc, rgb_tables, tab, NT, HdP):
         """x2 register engine, round 5: the ToRGB layers of the skip blocks as a NINTH output tile of each block's second
@@ -585,7 +585,7 @@ class SynthesisPlan:
         # (the choice looks at the rows of ONE item, never at the batch: a batch and its items alone take the same kernel and stay
         # bit-identical -- the x2 arithmetic behind it turns a 1e-6 difference of its input into 1e-4 of quantisation noise; every
         # shipped geometry has R >= 2048)
-        if feature_maps.is_cuda and os.environ.get("H3D_SHARED_GEMM", "x3") == "x3" and R >= 1024:
+        if feature_maps.is_cuda and R >= 1024:
             from ..components.ops import linear
             if linear._native_ok(self.ws_pixel.shape[0], F):
                 # the rendered maps arrive as a channel slice [.., 3:] of the [B,R,F+3] render output (row stride F + 3, 12 bytes

@@ -8,16 +8,10 @@ the following `view(size(0), -1).pow(2).sum(1).mean()` then averages the squared
 mode="per_sample" is the textbook ||grad_x D||^2 per sample (opt-in: about C times stronger at the same r1_lambda).  In
 the multi-GPU step either statistic is all-gathered across the ranks (parallel.r1_allgather).
 """
-import contextlib
-import os
-
 import torch
 import torch.nn.functional as F
 
 from ..components.ops import conv as conv_ops
-
-R1_INPUT_GRADS_ONLY = os.environ.get("H3D_R1_INPUT_GRADS_ONLY", "1") != "0"      # A/B switch (round 6)
-
 
 def logistic_d_loss(pred_real, pred_gen, gan_lambda=1.0):
     """softplus(D(fake)) + softplus(-D(real)), means over every prediction pixel (phase_trainer.py:388-389)."""
@@ -34,7 +28,7 @@ def r1_gradient(d_input_real, d_output_real, gan_lambda=1.0, scale=None):
         target = torch.softmax(d_output_real["segments"], dim=1).sum()
     # only the image's gradient is asked for: the native convolutions skip their weight / bias gradients in this pass (the engine
     # would drop them unread; ops/conv.py: input_grads_only)
-    with conv_ops.input_grads_only() if R1_INPUT_GRADS_ONLY else contextlib.nullcontext():
+    with conv_ops.input_grads_only():
         if scale is None or (not torch.is_tensor(scale) and scale == 1.0):
             return torch.autograd.grad(outputs=target, inputs=d_input_real, create_graph=True)[0]
         grad = torch.autograd.grad(outputs=target * scale, inputs=d_input_real, create_graph=True)[0]

@@ -500,7 +500,7 @@ int h3d_synthesis_x3(const void* stream, int64_t total_stages, const float* tabl
  * and the first skip block (block 3 of the shipped configurations: the base of the residual stream) may carry g_offset = 1 in both
  * of their SPADEs (the field is unused for pixel_style = 0): their convolutions' stages are then in the h3d_synthesis_x3 format
  * (bf16 hi | lo) and run on three bf16 products inside this kernel -- all such blocks or none.  SynthesisPlan.build_x3(x2=True)
- * does that by default (H3D_SYNTH_MID_X3=0: all-x2 stream). */
+ * does that by default (SynthesisPlan.X2_MID_X3 = False: all-x2 stream). */
 int h3d_synthesis_x2(const void* stream, int64_t total_stages, const float* tables, int table_floats,
                      const h3d_synth_desc* desc, const float* G, int g_channels, int Hr, int Wr,
                      const float* cst, int n_cst, const float* ab, int n_ab, float* rgb, int B, int H, int W,
