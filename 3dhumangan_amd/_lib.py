@@ -209,6 +209,16 @@ def need_cuda(*tensors):
                        f"wrap the call in `with torch.cuda.device({dev.index}):`")
 
 
+def canonical_device(device):
+    """torch.device of `device` with "cuda" / torch.device("cuda") resolved to the current device: the one spelling that
+    per-device caches key on, so that a cache filled through "cuda" is found by a call that asks with a tensor's device."""
+    import torch
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
 def stream_handle():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)

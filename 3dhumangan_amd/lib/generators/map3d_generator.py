@@ -26,7 +26,7 @@ from ..._stages import stage
 from ..components import smpl
 from ..components.ops.bias_act import bias_act
 from . import volume_rendering as vr
-from .differentiable import field_forward, synthesis_forward
+from .differentiable import synthesis_forward
 from .modsynth_pack import ModSynthesisPlan
 from .style_input_pack import StyleInputPlan
 from .synthesis_pack import SynthesisPlan
@@ -56,6 +56,47 @@ def _consume_camera_rng(sample_dist, batch, device):
         draw((batch, 1), device=device), draw((batch, 1), device=device)
     elif sample_dist == "truncated_gaussian":
         torch.empty((batch, 1, 4), device=device).normal_(), torch.empty((batch, 1, 4), device=device).normal_()
+
+
+def _integration_noise(given, shape, nerf_noise, device):
+    """The noise ray integration adds to the densities: `given` when it is injected, else drawn where the reference draws it
+    (volume_rendering.py:24) -- also when nerf_noise == 0 scales it away, which leaves None."""
+    if given is not None:
+        return given
+    drawn = torch.randn(shape, device=device)
+    return drawn * nerf_noise if nerf_noise != 0 else None
+
+
+def _render_route(differentiable, recording, hierarchical_sample, fused, train_field, fuse_geo, device_pack, precision, S,
+                  fused_supported, render_geo_supported):
+    """Which kernels a render call takes -> (route, field engine, differentiable).  Plain values only: `recording` is
+    torch.is_grad_enabled(), `device_pack` / `precision` are the field module's own settings and the two predicates its
+    fused_supported(S, engine) / render_geo_supported(S, engine).  First match:
+
+      hierarchical_sample, differentiable                      NotImplementedError
+      hierarchical_sample                                      "hierarchical"  coarse + fine pass on the unfused kernels
+      differentiable, nothing recording, fused, train_field x3 | x2, device_pack, precision f16x2 | f16x3 that fuses S
+                                                               promoted: engine f16x3 | f16x2 by train_field, not differentiable
+      fused, not differentiable, engine fuses S, fuse_geo, engine builds the geometry features
+                                                               "fused_geo"     nearest-vertex search + render_geo
+      fused, not differentiable, engine fuses S                "fused"         geometry features + render
+      otherwise                                                "unfused"       geometry features + field tensor + ray integration
+
+    Promotion: a train-mode forward that nothing records (the D step's no-grad generator forward, reference
+    lib/trainers/phase_trainer.py:355-362) runs the fused render on device-packed weights; whether S fuses is asked of the
+    module's own engine, the call then runs on train_field's."""
+    if hierarchical_sample:
+        if differentiable:
+            raise NotImplementedError("hierarchical_sample=True has no differentiable path (no shipped config trains with it)")
+        return "hierarchical", precision, False
+    engine = precision
+    if (differentiable and not recording and fused and train_field in ("x3", "x2") and device_pack
+            and precision in ("f16x2", "f16x3") and fused_supported(S, precision)):
+        engine, differentiable = "f16x3" if train_field == "x3" else "f16x2", False
+    can_fuse = fused and not differentiable and fused_supported(S, engine)
+    if can_fuse and fuse_geo and render_geo_supported(S, engine):
+        return "fused_geo", engine, differentiable
+    return "fused" if can_fuse else "unfused", engine, differentiable
 
 
 class LatentPool(nn.Module):
@@ -393,9 +434,7 @@ class Map3DGenerator(nn.Module):
     def synthesis_plan(self, device):
         """Packed synthesis weights for `device` ("cuda", "cuda:0" and torch.device("cuda", 0) name the same plan: an
         engine override set through one spelling must be seen by forward(), which asks with the tensors' device)."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = _lib.canonical_device(device)
         sd = self.state_dict()
         key = (str(device),) + tuple((v.data_ptr(), v._version) for n, v in sd.items()
                                      if n.startswith(("synthesis_network", "synthesis_input")))
@@ -408,9 +447,7 @@ class Map3DGenerator(nn.Module):
 
     def style_input_plan(self, device):
         """Packed `synthesis_style_input` weights for `device` (the disable_render=True path), cached per weight version."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = _lib.canonical_device(device)
         sd = {"synthesis_style_input." + n: v for n, v in self.synthesis_style_input.state_dict().items()}
         key = (str(device),) + tuple((v.data_ptr(), v._version) for v in sd.values())
         if self._style_plan is None or self._style_plan_key != key:
@@ -447,120 +484,76 @@ class Map3DGenerator(nn.Module):
     def _render(self, freq, phase, conditions, render_width, render_height, ray_start, ray_end, coarse_steps, fine_steps=None,
                 h_stddev=0, v_stddev=0, h_mean=0, v_mean=0, hierarchical_sample=False, sample_dist=None,
                 lock_view_dependence=False, staged=False, max_points=50000, jitter=None, noise=None, fused=True,
-                differentiable=False, **kwargs):
-        if hierarchical_sample and differentiable:
-            raise NotImplementedError("hierarchical_sample=True has no differentiable path (no shipped config trains with it)")
-        nf = self.neural_field
-        if (differentiable and not torch.is_grad_enabled() and not hierarchical_sample and fused and self.train_field in ("x3", "x2")
-                and nf.device_pack and nf.precision in ("f16x2", "f16x3") and nf.fused_supported(int(coarse_steps))):
-            keep, nf.precision = nf.precision, "f16x3" if self.train_field == "x3" else "f16x2"
-            try:
-                return self._render(freq, phase, conditions, render_width, render_height, ray_start, ray_end, coarse_steps, fine_steps,
-                                    h_stddev, v_stddev, h_mean, v_mean, False, sample_dist, lock_view_dependence, staged, max_points,
-                                    jitter, noise, fused, differentiable=False, **kwargs)
-            finally:
-                nf.precision = keep
-        if hierarchical_sample:
-            return self._render_hierarchical(freq, phase, conditions, render_width, render_height, ray_start, ray_end,
-                                             int(coarse_steps), int(coarse_steps if fine_steps is None else fine_steps),
-                                             lock_view_dependence, jitter, noise, sample_dist=sample_dist, **kwargs)
-        c = conditions
-        dev = freq.device
-        B, S = freq.shape[0], int(coarse_steps)
-        R = render_width * render_height
-        focals = c["intrinsics"][:, 0, 0]
-        scales = c["scales"].float()
+                differentiable=False, noise_coarse=None, fine_u=None, **kwargs):
+        nf, c, dev = self.neural_field, conditions, freq.device
+        B, S, R, res = freq.shape[0], int(coarse_steps), render_width * render_height, (render_width, render_height)
+        route, engine, differentiable = _render_route(differentiable, torch.is_grad_enabled(), hierarchical_sample, fused,
+                                                      self.train_field, self.fuse_geo, nf.device_pack, nf.precision, S,
+                                                      nf.fused_supported, nf.render_geo_supported)
+        focals, scales = c["intrinsics"][:, 0, 0], c["scales"].float()
+        mesh = (c["skeletons_xyz"], c["vertices"], c["tpose_vertices"], c["fk_matrices"], c["lbs_weights"])
+        nerf_noise, scaler = kwargs.get("nerf_noise", 0), 2.0 / self.side_length
+        integ = dict(clamp_mode=kwargs["clamp_mode"], last_back=kwargs.get("last_back", False), white_back=kwargs.get("white_back", False))
         # RNG order of the reference: jitter U(0,1) [B,R,S,1]; the discarded camera sample; integration noise randn
         with stage(self, "ray_setup"):
-            pts, z_vals = vr.sample_rays(focals, scales, c["cam2world_matrices"], S, (render_width, render_height),
-                                         ray_start, ray_end, jitter=jitter, perturb=True)
+            pts, z_vals = vr.sample_rays(focals, scales, c["cam2world_matrices"], S, res, ray_start, ray_end, jitter=jitter, perturb=True)
+            frame = vr.ray_frame_world(focals, c["cam2world_matrices"], res) if route == "hierarchical" else None
         _consume_camera_rng(sample_dist, B, dev)
-        nerf_noise = kwargs.get("nerf_noise", 0)
-        if noise is None:
-            drawn = torch.randn((B, R, S, 1), device=dev)                          # volume_rendering.py:24
-            noise = drawn * nerf_noise if nerf_noise != 0 else None
-        can_fuse = fused and not differentiable and self.neural_field.fused_supported(S)
-        # A4 inside the fused render (round 4): only the nearest-vertex search runs as its own kernel, the features are built in
-        # the field kernel's prologue -- the [B, N, 31] tensor is never written (H3D_FUSE_GEO=0: the two-kernel path)
-        geo_in = can_fuse and self.fuse_geo and self.neural_field.render_geo_supported(S)
-        with stage(self, "geo_features"):
-            if geo_in:
-                vik = smpl.vertex_inverse_transforms(c["fk_matrices"], c["lbs_weights"])
-                nn_index = smpl.nearest_vertex(pts, c["vertices"], ray_shape=(render_height, render_width, S))
-                geo = None
-            else:
-                geo = self.get_geo_features(pts, c["skeletons_xyz"], c["vertices"], c["tpose_vertices"], c["fk_matrices"],
-                                            c["lbs_weights"])
-        dirs = None
-        if not lock_view_dependence:
-            dirs = vr.ray_directions_world(focals, c["cam2world_matrices"], (render_width, render_height), S)
-        scaler = 2.0 / self.side_length
-        clamp_mode = kwargs["clamp_mode"]
-        last_back, white_back = kwargs.get("last_back", False), kwargs.get("white_back", False)
-        if geo_in:
-            with stage(self, "render_fused"):
-                feats, depths, weights = self.neural_field.render_geo(
-                    pts, freq, phase, nn_index, c["skeletons_xyz"], c["vertices"], c["tpose_vertices"], vik, dirs, z_vals, S,
-                    legacy_mode=self.legacy_mode, input_scaler=scaler, noise=noise, clamp_mode=clamp_mode,
-                    last_back=last_back, white_back=white_back)
-        elif differentiable:
-            with stage(self, "neural_field"):
-                field = field_forward(self.neural_field, pts, freq, phase, geo, dirs, input_scaler=scaler)
-            with stage(self, "ray_integrate"):
-                feats, depths, weights = vr.ray_integration(field.reshape(B, R, S, -1), z_vals, noise_std=0, noise=noise,
-                                                            clamp_mode=clamp_mode, last_back=last_back,
-                                                            white_back=white_back, consume_rng=False)
-        elif can_fuse:
-            with stage(self, "render_fused"):
-                feats, depths, weights = self.neural_field.render(pts, freq, phase, geo, dirs, z_vals, S,
-                                                                  input_scaler=scaler, noise=noise, clamp_mode=clamp_mode,
-                                                                  last_back=last_back, white_back=white_back)
+        if route == "hierarchical":
+            feats, depths, weights = self._render_hierarchical(freq, phase, mesh, pts, z_vals, frame, S if fine_steps is None else int(fine_steps),
+                                                               engine, lock_view_dependence, scaler, integ, nerf_noise, noise_coarse, fine_u, noise)
         else:
-            with stage(self, "neural_field"):
-                field = self.neural_field(pts, freq, phase, geo, dirs, input_scaler=scaler, differentiable=False)
-            with stage(self, "ray_integrate"):
-                feats, depths, weights = vr.ray_integration(field.reshape(B, R, S, -1), z_vals, noise_std=0, noise=noise,
-                                                            clamp_mode=clamp_mode, last_back=last_back,
-                                                            white_back=white_back, consume_rng=False)
+            noise = _integration_noise(noise, (B, R, S, 1), nerf_noise, dev)
+            # "fused_geo": A4 inside the fused render (round 4) -- only the nearest-vertex search runs as its own kernel, the features
+            # are built in the field kernel's prologue, the [B, N, 31] tensor is never written (H3D_FUSE_GEO=0: the two-kernel path)
+            with stage(self, "geo_features"):
+                if route == "fused_geo":
+                    vik = smpl.vertex_inverse_transforms(c["fk_matrices"], c["lbs_weights"])
+                    nn_index = smpl.nearest_vertex(pts, c["vertices"], ray_shape=(render_height, render_width, S))
+                else:
+                    geo = self.get_geo_features(pts, *mesh)
+            dirs = None if lock_view_dependence else vr.ray_directions_world(focals, c["cam2world_matrices"], res, S)
+            if route == "fused_geo":
+                with stage(self, "render_fused"):
+                    feats, depths, weights = nf.render_geo(pts, freq, phase, nn_index, *mesh[:3], vik, dirs, z_vals, S,
+                                                           legacy_mode=self.legacy_mode, input_scaler=scaler, noise=noise,
+                                                           precision=engine, **integ)
+            elif route == "fused":
+                with stage(self, "render_fused"):
+                    feats, depths, weights = nf.render(pts, freq, phase, geo, dirs, z_vals, S, input_scaler=scaler, noise=noise,
+                                                       precision=engine, **integ)
+            else:
+                with stage(self, "neural_field"):
+                    field = nf(pts, freq, phase, geo, dirs, input_scaler=scaler, differentiable=differentiable, precision=engine)
+                with stage(self, "ray_integrate"):
+                    feats, depths, weights = vr.ray_integration(field.reshape(B, R, S, -1), z_vals, noise_std=0, noise=noise,
+                                                                consume_rng=False, **integ)
         rgb_render = (feats[..., :3] * 2 - 1).reshape(B, render_height, render_width, 3).permute(0, 3, 1, 2)
         return rgb_render, feats[..., 3:], depths, weights, None
 
-    def _render_hierarchical(self, freq, phase, c, render_width, render_height, ray_start, ray_end, S, Sf,
-                             lock_view_dependence, jitter, noise, noise_coarse=None, fine_u=None, sample_dist=None,
-                             **kwargs):
-        """reference :449-516: coarse pass -> compositing weights -> importance samples -> fine pass -> merge by depth ->
-        integration over all samples.  The field tensors materialise here (unfused kernels); random tensors can be
-        injected (jitter, noise_coarse [B,R,S,1], fine_u [B*R,Sf], noise [B,R,S+Sf,1]) or are drawn where the reference
-        draws them."""
-        dev = freq.device
-        B, R = freq.shape[0], render_width * render_height
-        focals, scales = c["intrinsics"][:, 0, 0], c["scales"].float()
-        res = (render_width, render_height)
-        with stage(self, "ray_setup"):
-            pts, z_vals = vr.sample_rays(focals, scales, c["cam2world_matrices"], S, res, ray_start, ray_end, jitter=jitter,
-                                         perturb=True)
-            origins, ray_dirs = vr.ray_frame_world(focals, c["cam2world_matrices"], res)
-        _consume_camera_rng(sample_dist, B, dev)
-        nerf_noise = kwargs.get("nerf_noise", 0)
-        clamp_mode = kwargs["clamp_mode"]
-        scaler = 2.0 / self.side_length
-        mesh = (c["skeletons_xyz"], c["vertices"], c["tpose_vertices"], c["fk_matrices"], c["lbs_weights"])
+    def _render_hierarchical(self, freq, phase, mesh, pts, z_vals, frame, Sf, engine, lock_view_dependence, scaler, integ, nerf_noise,
+                             noise_coarse, fine_u, noise):
+        """reference :449-516, behind _render's ray set-up: coarse pass -> compositing weights -> importance samples -> fine pass ->
+        merge by depth -> integration over all samples -> (features, depths, weights).  The field tensors materialise here (unfused
+        kernels); random tensors can be injected (noise_coarse [B,R,S,1], fine_u [B*R,Sf], noise [B,R,S+Sf,1]) or are drawn where
+        the reference draws them."""
+        (B, R, S), dev = z_vals.shape[:3], freq.device
+        origins, ray_dirs = frame
 
-        def dirs_for(n_steps):
-            if lock_view_dependence:
-                return None
-            return ray_dirs.unsqueeze(2).expand(B, R, n_steps, 3).reshape(B, R * n_steps, 3).contiguous()
+        def field(points, n_steps):
+            with stage(self, "geo_features"):
+                geo = self.get_geo_features(points, *mesh)
+            with stage(self, "neural_field"):
+                dirs = None
+                if not lock_view_dependence:
+                    dirs = ray_dirs.unsqueeze(2).expand(B, R, n_steps, 3).reshape(B, R * n_steps, 3).contiguous()
+                return self.neural_field(points, freq, phase, geo, dirs, input_scaler=scaler, differentiable=False,
+                                         precision=engine).reshape(B, R, n_steps, -1)
 
-        with stage(self, "geo_features"):
-            geo = self.get_geo_features(pts, *mesh)
-        with stage(self, "neural_field"):
-            coarse = self.neural_field(pts, freq, phase, geo, dirs_for(S), input_scaler=scaler,
-                                       differentiable=False).reshape(B, R, S, -1)
-        if noise_coarse is None:
-            drawn = torch.randn((B, R, S, 1), device=dev)                          # volume_rendering.py:24, first call
-            noise_coarse = drawn * nerf_noise if nerf_noise != 0 else None
+        coarse = field(pts, S)
+        noise_coarse = _integration_noise(noise_coarse, (B, R, S, 1), nerf_noise, dev)        # first ray_integration call
         with stage(self, "ray_integrate"):
-            _, _, w = vr.ray_integration(coarse, z_vals, noise_std=0, noise=noise_coarse, clamp_mode=clamp_mode,
+            _, _, w = vr.ray_integration(coarse, z_vals, noise_std=0, noise=noise_coarse, clamp_mode=integ["clamp_mode"],
                                          consume_rng=False)
         with stage(self, "resample"):
             w = w.reshape(B * R, S) + 1e-5
@@ -568,22 +561,12 @@ class Map3DGenerator(nn.Module):
             z_mid = 0.5 * (zv[:, :-1] + zv[:, 1:])
             fine_z = vr.sample_pdf(z_mid, w[:, 1:-1], Sf, det=False, u=fine_u).reshape(B, R, Sf, 1)
             fine_pts = vr.ray_points(origins, ray_dirs, fine_z)
-        with stage(self, "geo_features"):
-            geo = self.get_geo_features(fine_pts, *mesh)
-        with stage(self, "neural_field"):
-            fine = self.neural_field(fine_pts, freq, phase, geo, dirs_for(Sf), input_scaler=scaler,
-                                     differentiable=False).reshape(B, R, Sf, -1)
+        fine = field(fine_pts, Sf)
         with stage(self, "resample"):
             all_out, all_z = vr.merge_samples(fine, coarse, fine_z, z_vals)
-        if noise is None:
-            drawn = torch.randn((B, R, S + Sf, 1), device=dev)                     # volume_rendering.py:24, second call
-            noise = drawn * nerf_noise if nerf_noise != 0 else None
+        noise = _integration_noise(noise, (B, R, S + Sf, 1), nerf_noise, dev)                 # second call
         with stage(self, "ray_integrate"):
-            feats, depths, weights = vr.ray_integration(all_out, all_z, noise_std=0, noise=noise, clamp_mode=clamp_mode,
-                                                        last_back=kwargs.get("last_back", False),
-                                                        white_back=kwargs.get("white_back", False), consume_rng=False)
-        rgb_render = (feats[..., :3] * 2 - 1).reshape(B, render_height, render_width, 3).permute(0, 3, 1, 2)
-        return rgb_render, feats[..., 3:], depths, weights, None
+            return vr.ray_integration(all_out, all_z, noise_std=0, noise=noise, consume_rng=False, **integ)
 
     def _synthesize(self, feature_maps, styles, render_hw, differentiable=False):
         if differentiable:

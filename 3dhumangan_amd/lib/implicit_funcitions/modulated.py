@@ -10,11 +10,40 @@ library GEMMs + the HIP film_sin kernels with hand-written adjoints.
 import ctypes
 import math
 import os
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
 
 from ... import _lib
+from ..generators.volume_rendering import _CLAMP
+
+
+class _Engine(NamedTuple):
+    """One arithmetic engine of the field: its entry points of the C ABI (include/h3d.h) and what a launch needs to know."""
+    name: str
+    pack_size: str
+    pack: str
+    device_pack: Optional[str]     # the packer's device-side twin (csrc/field_x3.hip: field_pack_kernel)
+    field: str
+    render: str                    # fused field + integration
+    render_geo: Optional[str]      # ... that builds the geometry features itself (A4 inside the render, csrc/field_x3.hip GEOIN)
+    tile: int                      # sample tile of the fused kernels
+    tier: tuple                    # extra trailing arguments (before the stream) of the field / render entry points
+
+
+_ENGINES = {e.name: e for e in (
+    _Engine("f16x3", "h3d_field_pack_x3_size", "h3d_field_pack_x3", "h3d_field_pack_x3_device", "h3d_neural_field_x3",
+            "h3d_render_fused_x3", "h3d_render_fused_x3_geo", 32, ()),
+    _Engine("f16x2", "h3d_field_pack_x2_size", "h3d_field_pack_x2", "h3d_field_pack_x2_device", "h3d_neural_field_x2",
+            "h3d_render_fused_x2", "h3d_render_fused_x2_geo", 32, ()),
+    _Engine("f16x3t", "h3d_field_pack_x3t_size", "h3d_field_pack_x3t", None, "h3d_neural_field_x3t", "h3d_render_fused_x3t", None, 64, ()),
+    _Engine("f16x1t", "h3d_field_pack_x3t_size", "h3d_field_pack_x3t", None, "h3d_neural_field_x3t_tier", "h3d_render_fused_x3t_tier",
+            None, 64, (1,)),
+    _Engine("f16x2t", "h3d_field_pack_x3t_size", "h3d_field_pack_x2t", None, "h3d_neural_field_x3t_tier", "h3d_render_fused_x3t_tier",
+            None, 64, (4,)),
+    _Engine("f32", "h3d_field_pack_size", "h3d_field_pack", None, "h3d_neural_field", "h3d_render_fused", None, 64, ()),
+)}
 
 
 class _Dense(nn.Module):
@@ -82,48 +111,33 @@ class COORDCONCATSIREN(nn.Module):
         return [self.first_layer_coord.layer, self.first_layer_mod.layer] + [d.layer for d in self.network] + \
                [self.sigma_layer, self.color_layer_sine.layer, self.color_layer_linear, self.feature_layer_linear]
 
-    # engine -> (pack-size, pack, field, fused-render) entry points of the C ABI, the sample tile of the fused kernel and
-    # the extra trailing arguments (before the stream) of the field / render entry points
-    _ENGINES = {
-        "f16x3": ("h3d_field_pack_x3_size", "h3d_field_pack_x3", "h3d_neural_field_x3", "h3d_render_fused_x3", 32, ()),
-        "f16x2": ("h3d_field_pack_x2_size", "h3d_field_pack_x2", "h3d_neural_field_x2", "h3d_render_fused_x2", 32, ()),
-        "f16x3t": ("h3d_field_pack_x3t_size", "h3d_field_pack_x3t", "h3d_neural_field_x3t", "h3d_render_fused_x3t", 64, ()),
-        "f16x1t": ("h3d_field_pack_x3t_size", "h3d_field_pack_x3t", "h3d_neural_field_x3t_tier", "h3d_render_fused_x3t_tier",
-                   64, (1,)),
-        "f16x2t": ("h3d_field_pack_x3t_size", "h3d_field_pack_x2t", "h3d_neural_field_x3t_tier", "h3d_render_fused_x3t_tier",
-                   64, (4,)),
-        "f32": ("h3d_field_pack_size", "h3d_field_pack", "h3d_neural_field", "h3d_render_fused", 64, ()),
-    }
+    def _engine(self, precision=None):
+        name = self.precision if precision is None else precision
+        if name not in _ENGINES:
+            raise ValueError(f"unknown precision {name!r}")
+        return _ENGINES[name]
 
-    # packers with a device-side twin (csrc/field_x3.hip: field_pack_kernel)
-    _DEVICE_PACKERS = {"h3d_field_pack_x3": "h3d_field_pack_x3_device", "h3d_field_pack_x2": "h3d_field_pack_x2_device"}
-
-    def _engine(self):
-        if self.precision not in self._ENGINES:
-            raise ValueError(f"unknown precision {self.precision!r}")
-        return self._ENGINES[self.precision]
-
-    def fused_supported(self, num_steps):
-        """Sample counts the fused field+integration kernel of the active engine accepts."""
-        S, tile = int(num_steps), self._engine()[4]
+    def fused_supported(self, num_steps, precision=None):
+        """Sample counts the fused field+integration kernel of the engine (None: the module's own) accepts."""
+        S, tile = int(num_steps), self._engine(precision).tile
         return (8 <= S <= tile and S & (S - 1) == 0) or (S > tile and S % tile == 0)
 
-    def packed_weights(self, device):
-        """Device blob in MFMA fragment order (csrc/field_common.hpp, csrc/field_x3.hip); cached until a
-        parameter changes."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+    def render_geo_supported(self, num_steps, precision=None):
+        return self._engine(precision).render_geo is not None and self.fused_supported(num_steps, precision)
+
+    def packed_weights(self, device, precision=None):
+        """Device blob in MFMA fragment order (csrc/field_common.hpp, csrc/field_x3.hip) for the engine (None: the module's own);
+        cached until a parameter changes."""
+        device = _lib.canonical_device(device)
         lins = self._params_for_pack()
-        size_name, pack_name = self._engine()[:2]
-        x3 = pack_name                       # engines that share a packer share the blob
-        key = (str(device), x3) + tuple((p.data_ptr(), p._version) for l in lins for p in (l.weight, l.bias))
-        hit = self._packed.get(x3)
+        eng = self._engine(precision)
+        key = (str(device), eng.pack) + tuple((p.data_ptr(), p._version) for l in lins for p in (l.weight, l.bias))
+        hit = self._packed.get(eng.pack)                 # engines that share a packer share the blob
         if hit is not None and hit[0] == key:
             return hit[1]
         lib = _lib.load()
         H, F = self.hidden_dim, self.feature_dim
-        on_device = (self.device_pack and pack_name in self._DEVICE_PACKERS and device.type == "cuda"
+        on_device = (self.device_pack and eng.device_pack is not None and device.type == "cuda"
                      and all(p.device == device for l in lins for p in (l.weight, l.bias)))
         if on_device:
             # round 6: packed where the parameters live (one memset + one launch, no synchronisation, bit-identical blob) -- what lets
@@ -141,26 +155,26 @@ class COORDCONCATSIREN(nn.Module):
         P.w_color, P.b_color = vp(host[7][0]), vp(host[7][1])
         P.w_rgb, P.b_rgb = vp(host[8][0]), vp(host[8][1])
         P.w_feat, P.b_feat = vp(host[9][0]), vp(host[9][1])
-        size_fn, pack_fn = getattr(lib, size_name), getattr(lib, pack_name)
-        nbytes = size_fn(H, F)
+        nbytes = getattr(lib, eng.pack_size)(H, F)
         if nbytes <= 0:
-            raise _lib.H3DError(f"field engine {self.precision} does not support widths {H}/{F}")
+            raise _lib.H3DError(f"field engine {eng.name} does not support widths {H}/{F}")
         if on_device:
             with torch.cuda.device(device):
                 dev_blob = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
-                rc = getattr(lib, self._DEVICE_PACKERS[pack_name])(ctypes.byref(P), H, F, _lib.ptr(dev_blob), _lib.stream_handle())
-            _lib.check(rc, self._DEVICE_PACKERS[pack_name])
+                rc = getattr(lib, eng.device_pack)(ctypes.byref(P), H, F, _lib.ptr(dev_blob), _lib.stream_handle())
+            _lib.check(rc, eng.device_pack)
         else:
             blob = torch.empty((nbytes + 3) // 4, dtype=torch.float32)
-            _lib.check(pack_fn(ctypes.byref(P), H, F, ctypes.c_void_p(blob.data_ptr())), "h3d_field_pack")
+            _lib.check(getattr(lib, eng.pack)(ctypes.byref(P), H, F, ctypes.c_void_p(blob.data_ptr())), "h3d_field_pack")
             dev_blob = blob.to(device)
-        self._packed[x3] = (key, dev_blob)
+        self._packed[eng.pack] = (key, dev_blob)
         return dev_blob
 
     def forward(self, input, frequencies, phase_shifts, geo_feature, ray_directions, input_scaler=1.,
-                geo_feature_scaler=1., differentiable=None, **kwargs):
+                geo_feature_scaler=1., differentiable=None, precision=None, **kwargs):
         """input [B,N,3], frequencies/phase_shifts [B,4H], geo_feature [B,N,31], ray_directions [B,N,3] or None
-        (None == the lock_view_dependence direction (0,0,-1))  ->  [B,N,F+4]."""
+        (None == the lock_view_dependence direction (0,0,-1))  ->  [B,N,F+4].  `precision`: the engine of the fused kernel for
+        this call (None: the module's own; the differentiable evaluation has one arithmetic)."""
         if self.training if differentiable is None else differentiable:
             from ..generators.differentiable import field_forward
             _lib.need_cuda(input, frequencies, phase_shifts, geo_feature, ray_directions)
@@ -173,10 +187,28 @@ class COORDCONCATSIREN(nn.Module):
                                  geo_feature_scaler)
         with torch.no_grad():
             return self._forward_fused(input, frequencies, phase_shifts, geo_feature, ray_directions, input_scaler,
-                                       geo_feature_scaler)
+                                       geo_feature_scaler, precision)
+
+    def _prepare(self, input, ray_directions, frequencies, phase_shifts, z_vals=None, num_steps=None, noise=None,
+                 clamp_mode="relu"):
+        """The operands every launch shares as contiguous fp32 -> (points, directions or None, frequencies, phases, render), where
+        `render` is None without z_vals and else (z_vals [B,R,S], noise [B,R,S] or None, the outputs features [B,R,F+3], depth
+        [B,R,1] and weights [B,R,S,1], the clamp code).  The caller binds all of it to locals until after its launch: _lib.ptr
+        keeps only the address, a temporary would be freed before the kernel runs (components/smpl.py: get_geo_features)."""
+        f32 = lambda t: None if t is None else t.contiguous().float()
+        pts, dirs, fr, ph = f32(input), f32(ray_directions), f32(frequencies), f32(phase_shifts)
+        if z_vals is None:
+            return pts, dirs, fr, ph, None
+        B, S = pts.shape[0], int(num_steps)
+        R = pts.shape[1] // S
+        z, nz = f32(z_vals.reshape(B, R, S)), None if noise is None else f32(noise.reshape(B, R, S))
+        feats = torch.empty((B, R, self.feature_dim + 3), device=pts.device, dtype=torch.float32)
+        depth = torch.empty((B, R, 1), device=pts.device, dtype=torch.float32)
+        weights = torch.empty((B, R, S, 1), device=pts.device, dtype=torch.float32)
+        return pts, dirs, fr, ph, (z, nz, feats, depth, weights, _CLAMP[clamp_mode])
 
     def _forward_fused(self, input, frequencies, phase_shifts, geo_feature, ray_directions, input_scaler=1.,
-                       geo_feature_scaler=1.):
+                       geo_feature_scaler=1., precision=None):
         unsq = input.dim() < 3
         if unsq:
             input, geo_feature = input.unsqueeze(1), geo_feature.unsqueeze(1)
@@ -184,72 +216,53 @@ class COORDCONCATSIREN(nn.Module):
         _lib.need_cuda(input, frequencies, phase_shifts, geo_feature, ray_directions)
         B, N, _ = input.shape
         H, F = self.hidden_dim, self.feature_dim
-        pts = input.contiguous().float()
+        eng = self._engine(precision)
+        pts, dirs, fr, ph, _ = self._prepare(input, ray_directions, frequencies, phase_shifts)
         geo = geo_feature if geo_feature_scaler == 1. else geo_feature * geo_feature_scaler
         geo = geo.contiguous().float()
-        dirs = None if ray_directions is None else ray_directions.contiguous().float()
-        fr, ph = frequencies.contiguous().float(), phase_shifts.contiguous().float()
         assert fr.shape == (B, 4 * H) and ph.shape == (B, 4 * H)
         out = torch.empty((B, N, F + 4), device=pts.device, dtype=torch.float32)
-        blob = self.packed_weights(pts.device)
-        fn = getattr(_lib.load(), self._engine()[2])
-        rc = fn(_lib.ptr(blob), _lib.ptr(pts), _lib.ptr(geo), _lib.ptr(dirs), _lib.ptr(fr),
-                                          _lib.ptr(ph), _lib.ptr(out), B, N, H, F, geo.shape[-1], float(input_scaler),
-                                          *self._engine()[5], _lib.stream_handle())
+        blob = self.packed_weights(pts.device, precision)
+        rc = getattr(_lib.load(), eng.field)(_lib.ptr(blob), _lib.ptr(pts), _lib.ptr(geo), _lib.ptr(dirs), _lib.ptr(fr), _lib.ptr(ph),
+                                             _lib.ptr(out), B, N, H, F, geo.shape[-1], float(input_scaler), *eng.tier,
+                                             _lib.stream_handle())
         _lib.check(rc, "h3d_neural_field")
         return out.squeeze(1) if unsq else out
 
     @torch.no_grad()
     def render(self, input, frequencies, phase_shifts, geo_feature, ray_directions, z_vals, num_steps, input_scaler=1.,
-               noise=None, clamp_mode="relu", last_back=False, white_back=False):
+               noise=None, clamp_mode="relu", last_back=False, white_back=False, precision=None):
         """Fused field evaluation + volume integration (reference: COORDCONCATSIREN.forward followed by
-        volume_rendering.ray_integration).  input [B,R*S,3] with the S samples of a ray contiguous.
-        -> (features [B,R,F+3], depth [B,R,1], weights [B,R,S,1])."""
+        volume_rendering.ray_integration) on the engine `precision` (None: the module's own).  input [B,R*S,3] with the S
+        samples of a ray contiguous.  -> (features [B,R,F+3], depth [B,R,1], weights [B,R,S,1])."""
         _lib.need_cuda(input, frequencies, phase_shifts, geo_feature, ray_directions, z_vals, noise)
-        B, N, _ = input.shape
-        S = int(num_steps)
-        R = N // S
-        H, F = self.hidden_dim, self.feature_dim
-        pts = input.contiguous().float()
+        eng = self._engine(precision)
+        pts, dirs, fr, ph, (z, nz, feats, depth, weights, mode) = self._prepare(input, ray_directions, frequencies, phase_shifts,
+                                                                                 z_vals, num_steps, noise, clamp_mode)
         geo = geo_feature.contiguous().float()
-        dirs = None if ray_directions is None else ray_directions.contiguous().float()
-        fr, ph = frequencies.contiguous().float(), phase_shifts.contiguous().float()
-        z = z_vals.reshape(B, R, S).contiguous().float()
-        nz = None if noise is None else noise.reshape(B, R, S).contiguous().float()
-        feats = torch.empty((B, R, F + 3), device=pts.device, dtype=torch.float32)
-        depth = torch.empty((B, R, 1), device=pts.device, dtype=torch.float32)
-        weights = torch.empty((B, R, S, 1), device=pts.device, dtype=torch.float32)
-        blob = self.packed_weights(pts.device)
-        mode = {"relu": 0, "softplus": 1}[clamp_mode]
-        fn = getattr(_lib.load(), self._engine()[3])
-        rc = fn(_lib.ptr(blob), _lib.ptr(pts), _lib.ptr(geo), _lib.ptr(dirs), _lib.ptr(fr),
-                                          _lib.ptr(ph), _lib.ptr(z), _lib.ptr(nz), _lib.ptr(feats), _lib.ptr(depth),
-                                          _lib.ptr(weights), B, R, S, H, F, geo.shape[-1], float(input_scaler), mode,
-                                          int(bool(last_back)), int(bool(white_back)), *self._engine()[5], _lib.stream_handle())
+        B, R, S = z.shape
+        blob = self.packed_weights(pts.device, precision)
+        rc = getattr(_lib.load(), eng.render)(_lib.ptr(blob), _lib.ptr(pts), _lib.ptr(geo), _lib.ptr(dirs), _lib.ptr(fr), _lib.ptr(ph),
+                                              _lib.ptr(z), _lib.ptr(nz), _lib.ptr(feats), _lib.ptr(depth), _lib.ptr(weights), B, R, S,
+                                              self.hidden_dim, self.feature_dim, geo.shape[-1], float(input_scaler), mode,
+                                              int(bool(last_back)), int(bool(white_back)), *eng.tier, _lib.stream_handle())
         _lib.check(rc, "h3d_render_fused")
         return feats, depth, weights
-
-    # engines whose fused kernel can build the geometry features itself (A4 inside the render, csrc/field_x3.hip GEOIN)
-    _GEO_ENGINES = {"f16x2": "h3d_render_fused_x2_geo", "f16x3": "h3d_render_fused_x3_geo"}
-
-    def render_geo_supported(self, num_steps):
-        return self.precision in self._GEO_ENGINES and self.fused_supported(num_steps)
 
     @torch.no_grad()
     def render_geo(self, input, frequencies, phase_shifts, nn_index, skeletons, vertices, tpose_vertices, vertex_ik,
                    ray_directions, z_vals, num_steps, legacy_mode=False, input_scaler=1., noise=None, clamp_mode="relu",
-                   last_back=False, white_back=False):
+                   last_back=False, white_back=False, precision=None):
         """`render` with the geometry features built inside the kernel (reference: get_geo_features,
         lib/components/smpl.py:210-249, then COORDCONCATSIREN.forward and ray_integration): instead of geo_feature [B,N,31] it
         takes nn_index [B,N] int32 (smpl.nearest_vertex), skeletons [B,24,3], vertices / tpose_vertices [B,V,3] and
         vertex_ik [B,V,16] (smpl.vertex_inverse_transforms).  -> (features [B,R,F+3], depth [B,R,1], weights [B,R,S,1])."""
         _lib.need_cuda(input, frequencies, phase_shifts, nn_index, skeletons, vertices, tpose_vertices, vertex_ik,
                        ray_directions, z_vals, noise)
+        eng = self._engine(precision)
+        if eng.render_geo is None:
+            raise ValueError(f"field engine {eng.name} has no fused render with in-kernel geometry")
         B, N, _ = input.shape
-        S = int(num_steps)
-        R = N // S
-        H, F = self.hidden_dim, self.feature_dim
-        pts = input.contiguous().float()
         idx = nn_index.contiguous()
         if idx.dtype != torch.int32 or tuple(idx.shape) != (B, N):
             raise ValueError("nn_index must be int32 [B, N]")
@@ -257,21 +270,16 @@ class COORDCONCATSIREN(nn.Module):
         tv, vik = tpose_vertices.contiguous().float(), vertex_ik.contiguous().float()
         if sk.shape[1:] != (24, 3) or vik.shape[1:] != (vt.shape[1], 16) or tv.shape != vt.shape:
             raise ValueError("skeletons [B,24,3], vertices / tpose_vertices [B,V,3], vertex_ik [B,V,16] expected")
-        dirs = None if ray_directions is None else ray_directions.contiguous().float()
-        fr, ph = frequencies.contiguous().float(), phase_shifts.contiguous().float()
-        z = z_vals.reshape(B, R, S).contiguous().float()
-        nz = None if noise is None else noise.reshape(B, R, S).contiguous().float()
-        feats = torch.empty((B, R, F + 3), device=pts.device, dtype=torch.float32)
-        depth = torch.empty((B, R, 1), device=pts.device, dtype=torch.float32)
-        weights = torch.empty((B, R, S, 1), device=pts.device, dtype=torch.float32)
-        blob = self.packed_weights(pts.device)
-        mode = {"relu": 0, "softplus": 1}[clamp_mode]
+        pts, dirs, fr, ph, (z, nz, feats, depth, weights, mode) = self._prepare(input, ray_directions, frequencies, phase_shifts,
+                                                                                 z_vals, num_steps, noise, clamp_mode)
+        _, R, S = z.shape
+        blob = self.packed_weights(pts.device, precision)
         lib = _lib.load()
         common = lambda b: (_lib.ptr(b), _lib.ptr(pts), _lib.ptr(idx), _lib.ptr(sk), _lib.ptr(vt), _lib.ptr(tv), _lib.ptr(vik),
                             vt.shape[1], int(bool(legacy_mode)), _lib.ptr(dirs), _lib.ptr(fr), _lib.ptr(ph), _lib.ptr(z), _lib.ptr(nz),
-                            _lib.ptr(feats), _lib.ptr(depth), _lib.ptr(weights), B, R, S, H, F, float(input_scaler), mode,
-                            int(bool(last_back)), int(bool(white_back)))
-        if self.precision == "f16x2" and self.refine_last_sample:
+                            _lib.ptr(feats), _lib.ptr(depth), _lib.ptr(weights), B, R, S, self.hidden_dim, self.feature_dim,
+                            float(input_scaler), mode, int(bool(last_back)), int(bool(white_back)))
+        if eng.name == "f16x2" and self.refine_last_sample:
             # Round 6: rays whose LAST sample's density lies within `refine_eps` of zero (relative to the ray's largest density, floored
             # by the density head's weight norm) are listed by the x2 launch and redone by the three-product engine right behind it:
             # the reference's delta = 1e9 on the last sample (lib/generators/volume_rendering.py:21) turns the SIGN of that density
@@ -281,17 +289,13 @@ class COORDCONCATSIREN(nn.Module):
             if buf is None or buf[0].device != pts.device or buf[0].shape != (B, cap):
                 buf = (torch.zeros(B, cap, dtype=torch.int32, device=pts.device), torch.zeros(B, dtype=torch.int32, device=pts.device))
                 self._refine_buf = buf
-            keep, self.precision = self.precision, "f16x3"
-            try:
-                blob3 = self.packed_weights(pts.device)           # the same weights in the x3 format (cached per weight version)
-            finally:
-                self.precision = keep
+            blob3 = self.packed_weights(pts.device, "f16x3")      # the same weights in the x3 format (cached per weight version)
             scale = self._sigma_scale(pts.device)
             rc = lib.h3d_render_fused_x2_geo_ref(*common(blob), float(self.refine_eps), scale, _lib.ptr(buf[0]), _lib.ptr(buf[1]), cap,
                                                  _lib.stream_handle())
             rc = rc or lib.h3d_render_fused_x3_geo_units(*common(blob3), _lib.ptr(buf[0]), _lib.ptr(buf[1]), cap, _lib.stream_handle())
         else:
-            rc = getattr(lib, self._GEO_ENGINES[self.precision])(*common(blob), _lib.stream_handle())
+            rc = getattr(lib, eng.render_geo)(*common(blob), _lib.stream_handle())
         _lib.check(rc, "h3d_render_fused_geo")
         return feats, depth, weights
 

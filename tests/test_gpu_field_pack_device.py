@@ -93,13 +93,15 @@ def test_unrecorded_train_forward_runs_the_fused_render(tier, tol_render, tol_rg
         G.train_field = mode
         calls = []
         keep = G.neural_field.render_geo
-        G.neural_field.render_geo = lambda *a, **k: (calls.append(G.neural_field.precision), keep(*a, **k))[1]
+        G.neural_field.render_geo = lambda *a, **k: (calls.append((k.get("precision", G.neural_field.precision),
+                                                                    G.neural_field.precision)), keep(*a, **k))[1]
         cond = {k: v.to(DEV) for k, v in g["cond"].items()}
         idx = g["latent_indices"].to(DEV) if "latent_indices" in g else None
         with torch.no_grad():
             out = G(g["z"].to(DEV), cond, latent_indices=idx, jitter=g["jitter"].to(DEV), noise=g["noise"].to(DEV), **cfg)
-        assert calls == ([] if mode == "off" else ["f16x3" if mode == "x3" else "f16x2"]), calls
-        assert G.neural_field.precision == "f16x2"                      # the engine choice of the call does not stick
+        # the call ran on the promoted engine, named per call: the module's own choice was not swapped on the way in ...
+        assert calls == ([] if mode == "off" else [("f16x3" if mode == "x3" else "f16x2", "f16x2")]), calls
+        assert G.neural_field.precision == "f16x2"                      # ... and the engine choice of the call does not stick
         assert rel_err(out["rgbs_render"].cpu(), g["out"]["rgbs_render"]) < tol_render
         assert rel_err(out["rgbs"].cpu(), g["out"]["rgbs"]) < tol_rgb
         sd = G.state_dict()
@@ -113,3 +115,48 @@ def test_unrecorded_train_forward_runs_the_fused_render(tier, tol_render, tol_rg
         rec = G(z, cond, latent_indices=idx, jitter=g["jitter"].to(DEV), noise=g["noise"].to(DEV), **cfg)
         assert calls == [] and rec["rgbs"].requires_grad
     assert rel_err(outs[tier]["rgbs"], outs["off"]["rgbs"]) < tol_rgb
+
+
+@pytest.mark.parametrize("tier", ["x3", "x2"])
+def test_the_promoted_render_is_the_eval_render_on_that_engine(tier):
+    """render(differentiable=True) that nothing records, promoted to the fused render of `train_field`'s engine, launches what the
+    eval-mode render launches when that engine is the module's own: same kernels, same inputs, same bits.  gen_tiny_mixed at its
+    own render size: in-kernel geometry on both engines, and for x2 the last-sample refinement, whose three-product launch asks
+    for a second engine's weights inside the promoted call."""
+    from conftest import load_golden
+    gens = importlib.import_module("3dhumangan_amd.lib.generators")
+    g = load_golden("gen_tiny_mixed")
+    cfg = dict(g["meta"])
+    cfg["neural_field_cls"] = impl.COORDCONCATSIREN
+    G = gens.Map3DGenerator(**cfg)
+    G.load_state_dict(g["state"], strict=True)
+    G = G.to(DEV).eval()
+    G.set_device(DEV)
+    nf = G.neural_field
+    nf.refine_last_sample, nf.refine_eps = True, 1e-3
+    cond = {k: v.to(DEV) for k, v in g["cond"].items()}
+    rk = {k: v for k, v in cfg.items() if k not in ("coarse_steps", "fine_steps", "render_width", "render_height")}
+    geo_calls = []
+    keep = nf.render_geo
+    nf.render_geo = lambda *a, **k: (geo_calls.append(k.get("precision", nf.precision)), keep(*a, **k))[1]
+
+    def render(**kw):
+        out = G.render(g["stage"]["freq"].to(DEV), g["stage"]["phase"].to(DEV), cond, cfg["render_width"], cfg["render_height"],
+                       coarse_steps=cfg["num_steps"], fine_steps=cfg["num_steps"], jitter=g["jitter"].to(DEV), noise=g["noise"].to(DEV),
+                       **kw, **rk)
+        units = None if tier == "x3" else nf.refined_units().clone()
+        return [t.clone() for t in out[:4]], units
+
+    engine = "f16x3" if tier == "x3" else "f16x2"
+    G.train_field, nf.precision = tier, "f16x2"
+    with torch.no_grad():
+        promoted, units_promoted = render(differentiable=True)
+    assert nf.precision == "f16x2"
+    nf.precision = engine
+    plain, units_plain = render()
+    assert nf.precision == engine and geo_calls == [engine, engine]
+    for name, a, b in zip(("rgb_render", "features", "depths", "weights"), promoted, plain):
+        assert torch.equal(a, b), f"{name}: max difference {float((a - b).abs().max()):.3e}"
+    assert rel_err(promoted[0].cpu(), g["out"]["rgbs_render"]) < (1e-4 if tier == "x3" else 1e-3)
+    if tier == "x2":
+        assert torch.equal(units_promoted, units_plain)
