@@ -26,6 +26,7 @@ from ..components.ops.film import film_sin
 from ..components.ops.linear import linear
 from ..components.ops.spade import spade_norm_act
 from ..components.ops.spectral import _SpectralWeight
+from ..components.ops.synth_input import synth_input
 from ..components.resample import bilinear_resize_cl, bilinear_resize_relu_cl
 
 # ------------------------------------------------------------------------------------------------ A5: the implicit function
@@ -110,10 +111,11 @@ def _resize_channels_last(t, render_hw, gen_hw, relu=False):
     return torch.relu(up) if relu else up
 
 
-def synthesis_forward(G, fmap_low, styles, render_hw, gen_hw, training, group=None, spade_kernels=None):
+def synthesis_forward(G, fmap_low, styles, render_hw, gen_hw, training, group=None, spade_kernels=None, block0=(None, None)):
     """SynthesisInput + bilinear resize + SynthesisNetwork (lib/generators/map3d_generator.py:58-97, 244-275;
     lib/components/map3d_layers.py:176-275, 346-352).  fmap_low [B,R,F] channels-last rendered features, styles [B,1,F]
-    -> rgb [B,3,H,W]."""
+    -> rgb [B,3,H,W].  block0 = (label map int64 [B,H,W] or None, latent [B,L] or None): the extra inputs of block 0
+    (2d_label_input / 2d_latent_input, :256-265); block 0 is then in_dim = F (+ L) wide, every later block hidden_dim."""
     sn = G.synthesis_network
     B, _, Fd = fmap_low.shape
     H, W = gen_hw
@@ -124,8 +126,13 @@ def synthesis_forward(G, fmap_low, styles, render_hw, gen_hw, training, group=No
     if mode not in ("all", "mixed", "isolated"):
         raise ValueError("invalid map3d_mode")
     conv_in = G.synthesis_input.network[0]
-    x0 = torch.sin(linear(_coords(H, W, dev, dt), conv_in.weight.flatten(1), conv_in.bias))      # [P, F]
-    x = x0.unsqueeze(0).expand(B, P, x0.shape[-1])
+    seg, z_in = block0
+    if seg is None and z_in is None:
+        x0 = torch.sin(linear(_coords(H, W, dev, dt), conv_in.weight.flatten(1), conv_in.bias))      # [P, F]
+        x = x0.unsqueeze(0).expand(B, P, x0.shape[-1])
+    else:
+        # per image: one HIP pass writes sine channels and latent channels side by side (ops/synth_input.py)
+        x = synth_input(conv_in.weight.flatten(1), conv_in.bias, (H, W), B, seg=seg, z=z_in, label_dim=G.label_dim).to(dt)
 
     def per_pixel(idx):
         return mode == "all" or idx in mod_blocks

@@ -11,6 +11,7 @@ differentiable path of lib/generators/differentiable.py runs instead, see Map3DG
     resize + synthesis input + 9 SPADE blocks + ToRGB      h3d_synthesis                  (A7, A8, A9)
     (spatial_normalization="none": 9 modulated-conv blocks + ToRGB      h3d_synthesis_mod)
     (disable_render=True: the rasterised body condition -> style feature map, no field / rays      h3d_style_input)
+    (2d_label_input / 2d_latent_input: label map / latent as inputs of block 0      h3d_synth_input + the layer-wise path)
 
 The reference forward is stochastic.  The draws happen here at the same places with torch's device
 RNG; ``jitter=`` / ``noise=`` kwargs inject explicit tensors instead (used by the parity tests).
@@ -364,17 +365,27 @@ class Map3DGenerator(nn.Module):
         # "x3" (default): three f16 products, the differentiable path's own error class (~1e-5); "x2": the inference default's tier;
         # "off": lib/generators/differentiable.py as in rounds 2-5.  The field has no batch statistics: train and eval mode coincide.
         self.train_field = os.environ.get("H3D_TRAIN_FIELD", "x3")
-        for flag in ("2d_semantic_input", "2d_label_input", "2d_latent_input"):
-            if k.get(flag, False):
-                raise NotImplementedError(f"{flag}=True is not used by any shipped config and has no HIP path")
+        # Block 0's input beyond "sine of the pixel coordinates" (reference :127-131, :140-141, :256-265): the label map as a third
+        # coordinate of synthesis_input, the latent as extra channels behind it.  2d_semantic_input widens synthesis_input by
+        # semantic_dim but the reference never concatenates the semantics: a no-op with semantic_dim == 0, a failing forward otherwise.
+        self.label_input, self.latent_input = bool(k.get("2d_label_input", False)), bool(k.get("2d_latent_input", False))
+        if k.get("2d_semantic_input", False) and k.get("semantic_dim", 0) > 0:
+            raise NotImplementedError("2d_semantic_input=True with semantic_dim > 0: the reference's own forward fails there (its "
+                                      "synthesis_input expects the semantics as channels but they are never concatenated)")
+        if k.get("spatial_normalization", "instance_norm") == "none":
+            for flag in ("2d_label_input", "2d_latent_input"):
+                if k.get(flag, False):
+                    raise NotImplementedError(f"{flag}=True with spatial_normalization='none': the modulated-conv engine takes "
+                                              "the coordinate input alone")
         self.neural_field = neural_field_cls(output_dim=k["feature_dim"] + 4, latent_dim=k["latent_dim"],
                                              input_dim=k["input_dim"], hidden_dim=k["hidden_dim"],
                                              geo_feature_dim=k["geo_feature_dim"], feature_dim=k["feature_dim"],
                                              num_blocks=k["neural_field_blocks"], device=None)
-        self.synthesis_input = _CoordInput(2, k["feature_dim"])
+        self.synthesis_input = _CoordInput(2 + int(self.label_input), k["feature_dim"])
         self.synthesis_style_input = _StyleInput(1 if "segments" in k["condition_modal_gen"] else 3, k["latent_dim"],
                                                  k["feature_dim"])
-        self.synthesis_network = SynthesisNetwork(input_dim=k["feature_dim"], style_dim=k["feature_dim"],
+        self.synthesis_network = SynthesisNetwork(input_dim=k["feature_dim"] + (k["latent_dim"] if self.latent_input else 0),
+                                                  style_dim=k["feature_dim"],
                                                   hidden_dim=k["hidden_dim"], num_blocks=k["synthesis_blocks"],
                                                   mod_blocks=k["mod_blocks"], map3d_mode=k.get("map3d_mode", "isolated"),
                                                   spatial_normalization=k.get("spatial_normalization", "instance_norm"))
@@ -568,13 +579,38 @@ class Map3DGenerator(nn.Module):
         with stage(self, "ray_integrate"):
             return vr.ray_integration(all_out, all_z, noise_std=0, noise=noise, consume_rng=False, **integ)
 
-    def _synthesize(self, feature_maps, styles, render_hw, differentiable=False):
-        if differentiable:
+    def _block0_inputs(self, latent, conditions, kwargs):
+        """What block 0 reads besides the pixel coordinates (reference :256-265 / :344-352) -> (label map int64 [B, H, W] or None,
+        latent [B, L] or None).  The flags are read from the call as in the reference and must be the ones the modules were built
+        with (the reference's convolutions would fail on the channel count)."""
+        for flag, built in (("2d_label_input", self.label_input), ("2d_latent_input", self.latent_input)):
+            if bool(kwargs.get(flag, False)) != built:
+                raise ValueError(f"{flag}={bool(kwargs.get(flag, False))} in the call, but the generator was built with {flag}={built}")
+        seg = None
+        if self.label_input:
+            seg = conditions["rasterized_segments"]
+            want = (latent.shape[0], self.gen_height, self.gen_width)
+            if tuple(seg.shape) != want:
+                raise ValueError(f"2d_label_input: rasterized_segments must be [batch, gen_height, gen_width] = {list(want)}, "
+                                 f"got {list(seg.shape)}")
+            seg = seg.long()
+        return seg, (latent if self.latent_input else None)
+
+    def _layerwise_synthesis(self):
+        """Input variants the fused engines do not take run layer by layer (differentiable.synthesis_forward) in inference too."""
+        return self.label_input or self.latent_input or self.feature_dim > self.hidden_dim
+
+    def _synthesize(self, feature_maps, styles, render_hw, differentiable=False, block0=(None, None)):
+        if differentiable or (self._layerwise_synthesis() and self.synthesis_network.normalization != "none"):
             if self.synthesis_network.normalization == "none":
                 raise NotImplementedError("spatial_normalization='none' has no differentiable synthesis path")
             with stage(self, "synthesis"):
-                return synthesis_forward(self, feature_maps, styles, render_hw, (self.gen_height, self.gen_width),
-                                         training=self.training, group=getattr(self, "process_group", None))
+                if differentiable:
+                    return synthesis_forward(self, feature_maps, styles, render_hw, (self.gen_height, self.gen_width),
+                                             training=self.training, group=getattr(self, "process_group", None), block0=block0)
+                with torch.no_grad():          # inference: running statistics, stored spectral-norm u / v, nothing recorded
+                    return synthesis_forward(self, feature_maps, styles, render_hw, (self.gen_height, self.gen_width),
+                                             training=False, block0=block0)
         plan = self.synthesis_plan(feature_maps.device)
         return plan.run(feature_maps, styles.reshape(styles.shape[0], -1), render_hw, (self.gen_height, self.gen_width),
                         owner=self)
@@ -632,8 +668,9 @@ class Map3DGenerator(nn.Module):
                 return {"rgbs": rgb_render, "rgbs_render": rgb_render}
             with stage(self, "mapping"):
                 _, styles = self.synthesis_mapping_network(latent)
+            block0 = self._block0_inputs(latent, conditions, kwargs)
             fmap, cond_hw = self._style_features(latent, conditions, kwargs)
-            return {"rgbs": self._synthesize(fmap, styles, cond_hw), "rgbs_render": rgb_render}
+            return {"rgbs": self._synthesize(fmap, styles, cond_hw, block0=block0), "rgbs_render": rgb_render}
         if differentiable and self.synthesis_network.normalization == "none":
             raise NotImplementedError("spatial_normalization='none' has the fused inference engine only: the training / "
                                       "differentiable path is not implemented (call .eval() and leave differentiable unset)")
@@ -647,7 +684,8 @@ class Map3DGenerator(nn.Module):
                                                 **rk)
         if kwargs.get("disable_synthesis", False):
             return {"rgbs": rgb_render, "rgbs_render": rgb_render}
-        rgb = self._synthesize(fmap, styles, (render_height, render_width), differentiable)
+        rgb = self._synthesize(fmap, styles, (render_height, render_width), differentiable,
+                               block0=self._block0_inputs(latent, conditions, kwargs))
         return {"rgbs": rgb, "rgbs_render": rgb_render}
 
     @torch.no_grad()
@@ -694,7 +732,9 @@ class Map3DGenerator(nn.Module):
             out = {"rgbs": bilinear_resize(rgb_render.contiguous(), (self.gen_height, self.gen_width)),
                    "rgbs_render": rgb_render}
         else:
-            out = {"rgbs": self._synthesize(fmap, styles, feature_hw), "rgbs_render": rgb_render}
+            # reference :300, :349-352: the TRUNCATED latent is the one block 0 reads
+            out = {"rgbs": self._synthesize(fmap, styles, feature_hw, block0=self._block0_inputs(latent, conditions, kwargs)),
+                   "rgbs_render": rgb_render}
         zc = conditions["intrinsics"][:, 0, 0] / conditions["scales"].float()
         depth = ((depths - zc.view(B, 1, 1)) / (kwargs["depth_length"] / 2.0)).clamp(-1.0, 1.0)
         depth_map = depth.reshape(B, render_height, render_width).unsqueeze(1).contiguous()

@@ -39,6 +39,11 @@ def _pad(v, n):
     return out
 
 
+def _grow(t, n):
+    """t with zero rows appended up to n of them."""
+    return torch.cat([t, t.new_zeros((n - t.shape[0],) + tuple(t.shape[1:]))], dim=0)
+
+
 class _Table:
     """A flat fp32 table under construction: add() appends a tensor and returns its offset in floats.  align = 4 pads every
     entry to whole float4s (the x3 / x3t kernels read their tables 16 bytes at a time), align = 1 leaves the fp32 engine's blob
@@ -107,11 +112,17 @@ class SynthesisPlan:
             raise ValueError("invalid map3d_mode")
         self.mode = map3d_mode
         self.n_blocks = n_blocks
-        C = g(f"{prefix}.network.m3d_0.conv_0.weight_orig").shape[0]
+        C, Cin = g(f"{prefix}.network.m3d_0.conv_0.weight_orig").shape[:2]
         F = g(f"{prefix}.network.m3d_0.spade_0.mlp_shared.0.weight").shape[1]
-        if g(f"{prefix}.network.m3d_0.conv_0.weight_orig").shape[1] != C:
-            raise NotImplementedError("synthesis kernel needs input_dim == hidden_dim (true for every shipped config)")
-        self.C, self.F = C, F
+        if Cin > C or g(f"{input_prefix}.network.0.weight").shape[:2] != (Cin, 2):
+            raise NotImplementedError("the fused synthesis engines take the coordinate input alone, input_dim <= hidden_dim wide "
+                                      "(a wider input, the label map or the latent as inputs run layer by layer: "
+                                      "differentiable.synthesis_forward)")
+        # input_dim < hidden_dim (feature_dim narrower than the network): block 0's input side is zero-padded to C, exactly --
+        # w_in / b_in rows zero (the in-kernel sin(0) = 0), the first SPADE's scale / shift, gamma / beta rows and biases zero on
+        # the padded channels (its table holds 1 + gamma's bias: that entry is zero as well), conv_0's padded K columns zero.
+        # Every engine then sees an ordinary C-wide network.
+        self.C, self.F, self.Cin = C, F, Cin
         HdP = (C + 31) // 32 * 32
         self.HdP = HdP
         NT, KBH = HdP // 32, HdP // 8
@@ -119,7 +130,8 @@ class SynthesisPlan:
         add = tab.add
         desc = SynthDesc()
         desc.n_blocks, desc.C = n_blocks, C
-        self._w_in, self._b_in = g(f"{input_prefix}.network.0.weight").reshape(C, 2), g(f"{input_prefix}.network.0.bias")
+        self._w_in = _grow(g(f"{input_prefix}.network.0.weight").reshape(Cin, 2), C)
+        self._b_in = _grow(g(f"{input_prefix}.network.0.bias"), C)
         _add_coord_input(tab, desc, self._w_in, self._b_in, HdP)
         ws_all, bs_all, self.pixel_ids, self.const_ids = [], [], [], []
         self._raw = []          # per SPADE: dict of dense fp32 tensors (consumed by the x3 builder)
@@ -138,11 +150,16 @@ class SynthesisPlan:
                 bs_all.append(g(sp + ".mlp_shared.0.bias"))
                 sc = g(sp + ".first_norm.weight") * torch.rsqrt(g(sp + ".first_norm.running_var") + EPS_BN)
                 sh = g(sp + ".first_norm.bias") - g(sp + ".first_norm.running_mean") * sc
-                wgam = g(sp + ".mlp_gamma.weight").reshape(C, SHARED)
-                wbet = g(sp + ".mlp_beta.weight").reshape(C, SHARED)
+                cin = Cin if sid == 0 else C
+                wgam = g(sp + ".mlp_gamma.weight").reshape(cin, SHARED)
+                wbet = g(sp + ".mlp_beta.weight").reshape(cin, SHARED)
                 bgam, bbet = g(sp + ".mlp_gamma.bias"), g(sp + ".mlp_beta.bias")
-                w = g(cv + ".weight_orig").reshape(C, C)
+                w = g(cv + ".weight_orig").reshape(C, cin)
                 sigma = torch.dot(g(cv + ".weight_u"), torch.mv(w, g(cv + ".weight_v")))
+                if cin < C:
+                    sc, sh, wgam, wbet, bbet = (_grow(t, C) for t in (sc, sh, wgam, wbet, bbet))
+                    bgam = torch.cat([bgam, bgam.new_full((C - cin,), -1.0)])      # 1 + bias is what the tables hold
+                    w = torch.cat([w, w.new_zeros(C, C - cin)], dim=1)
                 self._raw.append(dict(pixel=pixel, conv_w=w / sigma, conv_b=g(cv + ".bias"), wgam=wgam, bgam=bgam,
                                       wbet=wbet, bbet=bbet, sc=sc, sh=sh))
                 d = bd.spade[s]

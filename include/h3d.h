@@ -683,6 +683,25 @@ int h3d_ray_integrate_bwd(const float* field, const float* z_vals, const float* 
                           const float* g_depth, const float* g_weights, float* d_field, int64_t n_rays, int S, int C,
                           int clamp_mode, int last_back, int white_back, h3d_stream_t stream);
 
+/* Block-0 input of the synthesis network with the label map and / or the latent as extra inputs (2d_label_input,
+ * 2d_latent_input; lib/generators/map3d_generator.py:256-265, lib/components/map3d_layers.py:241-275), channels last, fp32:
+ *     out[b, p, n]     = sin(w[n,0] i + w[n,1] j + w[n,2] lab + bias[n])      n < F
+ *     out[b, p, F + l] = z[b, l]                                              l < L   (L = 0, z NULL: no latent channels)
+ * with p = y W + x, i = linspace(-1, 1, H)[y], j = linspace(-1, 1, W)[x], lab = float(seg[b, p]) / label_dim * 2 - 1 (fp32, a true
+ * division).  w [F, K] row-major, K = 3 with seg int64 [B, H, W], K = 2 with seg NULL; out [B, H*W, F + L].
+ * h3d_synth_input_bwd: given dx [B, H*W, F + L] contiguous, da = dx[..., :F] * cos(argument) with the argument recomputed;
+ *     dw [F, K] = sum da (i, j, lab),  db [F] = sum da,  dz [B, L] = sum_p dx[b, p, F + l]   (no gradient to the labels).
+ * Deterministic, no atomics: per-workgroup sums into partial [B, nblk, 4, F] and partial_z [B, nblk, L]
+ * (nblk = ceil(H*W / h3d_synth_input_rows())), then a second pass adds them in a fixed order.  partial_z and dz may both be NULL.
+ * H3D_EINVAL: null pointer, K outside {2, 3}, seg given with K == 2 or missing with K == 3, B > 65535, H*W >= 2^31 - 512.
+ */
+int h3d_synth_input_rows(void);
+int h3d_synth_input(const float* w, const float* bias, const int64_t* seg, const float* z, float* out, int B, int H, int W,
+                    int F, int L, int K, int label_dim, h3d_stream_t stream);
+int h3d_synth_input_bwd(const float* w, const float* bias, const int64_t* seg, const float* dx, float* partial,
+                        float* partial_z, float* dw, float* db, float* dz, int B, int H, int W, int F, int L, int K,
+                        int label_dim, h3d_stream_t stream);
+
 /* Zero-padded channels, channels-last:  out[b][p][c] = in[b*sb + c*sc + p*sp] for c < Cin, 0 for Cin <= c < Cout  (out [B, HW, Cout]
  * contiguous, 16-byte aligned, Cout % 4 == 0; element strides sb, sc, sp: any input layout; dtype 0 = f32, 1 = f16).  The padding in
  * front of a native convolution with a channel count that is not a multiple of 64 (the discriminator's RGB stem,
