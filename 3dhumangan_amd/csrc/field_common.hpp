@@ -18,7 +18,7 @@
 // k-block (8 k) ahead.  MFMA k-step e of block kb therefore contracts k = 8*kb + e (lanes 0-31) and
 // k = 8*kb + 4 + e (lanes 32-63); A is read with the same mapping.
 #pragma once
-#include "common.hpp"
+#include "device_helpers.hpp"
 
 namespace h3d {
 

@@ -34,6 +34,7 @@
 // tests/x2_emulation.py, tests/test_x2_error_model_cpu.py (2e-5 at the operator boundary at width 256).
 #include "x3_common.hpp"
 #include "field_pack.hpp"
+#include "composite.hpp"
 #include <string.h>
 #include <math.h>
 #include <stdio.h>
@@ -138,17 +139,6 @@ struct Args {
 constexpr int kHeadPad = 64;       // bytes behind every head's fragment rows in LDS (bank staggering)
 constexpr int kJointRows = 40;     // GEOIN: LDS table of 3 + 24 + 13 float4 rows (joints at rows 3..26, zeros around them)
 
-// the oracle's squared distance, (dx*dx + dy*dy) + dz*dz without contraction (geo_features.hip: sqdist_exact)
-__device__ __forceinline__ float sqdist_exact(float px, float py, float pz, float vx, float vy, float vz) {
-    const float dx = __fsub_rn(px, vx), dy = __fsub_rn(py, vy), dz = __fsub_rn(pz, vz);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-
-__device__ __forceinline__ float density(float x, int clamp_mode) {
-    if (clamp_mode == 1) return x > 20.f ? x : log1pf(expf(x));
-    return fmaxf(x, 0.f);
-}
-
 // two fp32 activations -> packed f16 hi halves (returned) and packed f16 lo halves, plain (non-packed) VALU only:
 // VOP3P instructions (v_pk_*, v_fma_mix) beside MFMAs cost several times their issue slot on this chip, and hipcc's SLP
 // vectoriser would turn the two subtractions into one v_pk_add_f32, hence the asm.
@@ -164,14 +154,6 @@ __device__ __forceinline__ unsigned split2_act(float a, float b, unsigned& lo) {
 
 // x2: the lo halves travel multiplied by rho = 2^12 (they only feed the fp6 conversion and the heads' scaled plane)
 __device__ __forceinline__ unsigned split2_act_x2(float a, float b, unsigned& lo) { return split2_x2_bounded(a, b, lo); }   // |sin| <= 1
-
-// two fp32 (already scaled) -> packed f16 hi halves (returned) and packed f16 lo halves
-__device__ __forceinline__ unsigned split2_f16(float a, float b, unsigned& lo) {
-    const half2v h2 = __builtin_convertvector(f32x2{a, b}, half2v);
-    const float fa = (float)h2.x, fb = (float)h2.y;
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a - fa, b - fb}, half2v));
-    return __builtin_bit_cast(unsigned, h2);
-}
 
 // 8 fp32 values of one lane -> hi / lo B-fragments
 __device__ __forceinline__ void split8(const float (&v)[8], float scale, half8& fh, half8& fl) {
@@ -482,7 +464,8 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
     float smax = 0.f;                                       // largest |density| of the unit's rays so far (ref_mode 1)
     auto ray_of = [&](int64_t nn) -> int64_t { return A.log2S < 0 ? unit_ray : (int64_t)b * A.R + (nn >> A.log2S); };
 
-    float carryT = 1.f, carryW = 0.f, carryD = 0.f, rgbacc = 0.f;
+    RayCarry carry;
+    float rgbacc = 0.f;
     float rayacc[NT];
 #pragma unroll
     for (int i = 0; i < NT; ++i) rayacc[i] = 0.f;
@@ -623,44 +606,17 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
         } else {
             // compositing weights of these 32 samples (both lane halves compute identical values)
             const int s_idx = A.log2S < 0 ? si * 32 + m : (int)(n & (S - 1));
-            float alpha = 0.f, f = 1.f, z = 0.f;
+            Sample sm;
             float last_abs = -1.f;                          // |density| of a ray's last sample held by this lane (ref_mode 1), else -1
             if (ok) {
-                z = a_z[gi];
-                const float delta = (s_idx == S - 1) ? 1e9f : a_z[gi + 1] - z;
-                const float sgn = sigma + (a_noise ? a_noise[gi] : 0.f);
-                alpha = 1.f - expf(-delta * density(sgn, A.clamp_mode));
-                f = (1.f - alpha) + 1e-12f;
+                sm = composite_sample(sigma, a_z, a_noise, gi, s_idx == S - 1, A.clamp_mode);
                 if (ref_mode == 1) {
-                    smax = fmaxf(smax, fabsf(sgn));
-                    if (s_idx == S - 1) last_abs = fabsf(sgn);
+                    smax = fmaxf(smax, fabsf(sm.sg));
+                    if (s_idx == S - 1) last_abs = fabsf(sm.sg);
                 }
             }
-            const int sl = m & (seglen - 1);
-            float incl = f;
-            for (int off = 1; off < seglen; off <<= 1) {
-                const float u = __shfl_up(incl, off, 32);
-                if (sl >= off) incl *= u;
-            }
-            float excl = __shfl_up(incl, 1, 32);
-            if (sl == 0) excl = 1.f;
-            w = alpha * (carryT * excl);
-            float wsum = w, dsum = w * z;
-            for (int off = seglen >> 1; off > 0; off >>= 1) {
-                wsum += __shfl_xor(wsum, off, 32);
-                dsum += __shfl_xor(dsum, off, 32);
-            }
-            const float z_last = __shfl(z, m | (seglen - 1), 32);
-            carryT *= __shfl(incl, 31, 32);
-            carryW += wsum;
-            carryD += dsum;
-            if (last_step) {
-                bg = 1.f - carryW;
-                if (ok && s_idx == S - 1) {
-                    if (h == 0) a_depth[ray_of(n)] = carryD + bg * z_last;
-                    if (A.last_back) w += bg;
-                }
-            }
+            w = composite_step<32>(sm, carry, m, seglen, last_step, ok && s_idx == S - 1, A.last_back, bg,
+                                   [&](float d) __attribute__((always_inline)) { if (h == 0) a_depth[ray_of(n)] = d; });
             if (ok && h == 0) a_weights[gi] = w;
             if (h == 0) { wl_lds[m] = w; wl_lds[32 + m] = bg; }
             if (ref_mode == 1 && last_step) {

@@ -15,6 +15,7 @@
 // exists in HBM.  MFMA-bound: 2*(7*Hd^2 + 41*Hd) flop per sample (x3 products issued).
 #include "x3t_common.hpp"
 #include "field_pack.hpp"
+#include "composite.hpp"
 #include <algorithm>
 #include <math.h>
 #include <stdio.h>
@@ -94,11 +95,6 @@ struct Args {
     float input_scaler;
     LayoutT L;
 };
-
-__device__ __forceinline__ float density(float x, int clamp_mode) {
-    if (clamp_mode == 1) return x > 20.f ? x : log1pf(expf(x));
-    return fmaxf(x, 0.f);
-}
 
 // P: partial products per operand pair of the hidden GEMMs (x3t_common.hpp): 3 = fp32-class (the default engine), 1 = plain
 // f16 matrix-core arithmetic (the "f16 MFMA" tier of BASELINE config 5; the K=3 / K=31 input layers always run with 3).
@@ -456,29 +452,23 @@ __global__ __launch_bounds__(256, 1) void field_x3t_kernel(Args A) {
                 // ---- compositing weights of the 64 samples of this tile (volume_rendering.py:18-46)
                 const int s_idx = (int)(n % S);
                 const int64_t gi = (int64_t)b * N + n;
-                float alpha = 0.f, f = 1.f, z = 0.f;
-                if (ok) {
-                    z = A.z_vals[gi];
-                    const float delta = (s_idx == S - 1) ? 1e9f : A.z_vals[gi + 1] - z;
-                    const float sg = sigma + (A.noise ? A.noise[gi] : 0.f);
-                    alpha = 1.f - expf(-delta * density(sg, A.clamp_mode));
-                    f = (1.f - alpha) + 1e-12f;
-                }
+                Sample sm;
+                if (ok) sm = composite_sample(sigma, A.z_vals, A.noise, gi, s_idx == S - 1, A.clamp_mode);
                 const int sl = t & (seglen - 1);
-                float incl = f;
+                float incl = sm.f;
                 for (int off = 1; off < seglen; off <<= 1) {
                     const float u = __shfl_up(incl, off, 64);
                     if (sl >= off) incl *= u;
                 }
                 float excl = __shfl_up(incl, 1, 64);
                 if (sl == 0) excl = 1.f;
-                float w = alpha * (carryT * excl);
-                float wsum = w, dsum = w * z;
+                float w = sm.alpha * (carryT * excl);
+                float wsum = w, dsum = w * sm.z;
                 for (int off = seglen >> 1; off > 0; off >>= 1) {
                     wsum += __shfl_xor(wsum, off, 64);
                     dsum += __shfl_xor(dsum, off, 64);
                 }
-                const float z_last = __shfl(z, t | (seglen - 1), 64);
+                const float z_last = __shfl(sm.z, t | (seglen - 1), 64);
                 carryT *= __shfl(incl, 63, 64);
                 carryW += wsum;
                 carryD += dsum;

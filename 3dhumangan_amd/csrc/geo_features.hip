@@ -35,7 +35,10 @@
 // fourth LDS plane), which is what "first index wins" means for the unsorted mesh.  The chunk nearest to the wave's centroid is
 // scanned first, so `run` is tight from the start: measured on the bench workload a wave scans ~22 % of the chunks
 // (tests/test_nn_pruning_cpu.py models the rule; the GPU tests compare indices with the oracle's brute force).
-#include "common.hpp"
+#include "device_helpers.hpp"
+
+using h3d::split2_f16;
+using h3d::sqdist_exact;
 
 namespace {
 
@@ -45,25 +48,11 @@ constexpr int kJoints = 24;
 constexpr int kChunk = 64;                 // vertices per filter chunk
 constexpr int kCand = 6;                   // remembered candidate chunks per point (8 until round 4: the sorted kernels need the registers)
 
-typedef float f2 __attribute__((ext_vector_type(2)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f16v __attribute__((ext_vector_type(16)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 typedef int i4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-
-// two fp32 -> packed f16 hi halves (returned) and packed f16 lo halves (residuals)
-__device__ __forceinline__ unsigned split2_f16(float a, float b, unsigned& lo) {
-    const half2v h2 = __builtin_convertvector(f2{a, b}, half2v);
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f2{a - (float)h2.x, b - (float)h2.y}, half2v));
-    return __builtin_bit_cast(unsigned, h2);
-}
-
-__device__ __forceinline__ float sqdist_exact(float px, float py, float pz, float vx, float vy, float vz) {
-    const float dx = __fsub_rn(px, vx), dy = __fsub_rn(py, vy), dz = __fsub_rn(pz, vz);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
 
 // exact scan of vertices [v4_begin*4, v4_end*4): the smallest distance, and among exact minima the smallest vertex index.
 // Unsorted mesh (ids == null): position = index, ascending scan, strict "<".  Sorted mesh: ids holds the original index of

@@ -11,22 +11,14 @@
 //           consecutive lanes read consecutive 16-byte slots across G whole rows per step (coalesced) and
 //           every thread keeps one float4 accumulator.  G partial sums meet in LDS.
 // Algorithmic bytes per ray: 4*(S*(C+1) [field] + S [z] + S [weights] + C [features] + 1 [depth]).
-#include "common.hpp"
+#include "composite.hpp"
+#include "device_helpers.hpp"
+
+using namespace h3d;
 
 namespace {
 
 constexpr int kThreads = 256;
-
-__device__ __forceinline__ float density(float x, int clamp_mode) {
-    if (clamp_mode == 1) return x > 20.f ? x : log1pf(expf(x));   // F.softplus (beta=1, threshold=20)
-    return fmaxf(x, 0.f);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // Wave 0 only.  Writes w[0..S) (with the last_back fix-up applied when requested), weights_out, depth.
 // Returns the background term 1 - sum(w) computed BEFORE the last_back update (volume_rendering.py:36,48).
@@ -39,28 +31,15 @@ __device__ __forceinline__ float scan_weights(const float* __restrict__ sig_base
     for (int s0 = 0; s0 < S; s0 += 64) {
         const int s = s0 + lane;
         const bool ok = s < S;
-        float f = 1.f, alpha = 0.f, zz = 0.f;
-        if (ok) {
-            float sg = sig_base[(int64_t)s * sig_stride];
-            if (noise) sg += noise[s];
-            zz = z[s];
-            const float delta = (s == S - 1) ? 1e9f : z[s + 1] - zz;
-            alpha = 1.f - expf(-delta * density(sg, clamp_mode));
-            f = (1.f - alpha) + 1e-12f;
-        }
-        float incl = f;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const float t = __shfl_up(incl, off, 64);
-            if (lane >= off) incl *= t;
-        }
-        float excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 1.f;
-        const float w = alpha * (carry * excl);
-        carry *= __shfl(incl, 63, 64);
+        Sample sm;
+        if (ok) sm = composite_sample(sig_base[(int64_t)s * sig_stride], z, noise, s, s == S - 1, clamp_mode);
+        const float incl = scan_inclusive<64>(sm.f, lane, 64);
+        const float excl = scan_exclusive<64>(incl, lane);
+        const float w = sm.alpha * (carry * excl);
+        carry *= tile_product<64>(incl);
         if (ok) w_lds[s] = w;
         wsum += w;
-        dsum += w * zz;
+        dsum += w * sm.z;
     }
     wsum = wave_sum(wsum);
     dsum = wave_sum(dsum);

@@ -8,18 +8,14 @@
 // 220 in tiny kernels.  Here: four launches forward, two backward, every reduction two-stage in a fixed order (deterministic).
 //   h3d_spectral_norm      sn_wtu (partial W^T u per 16 rows) -> sn_treduce (t, partial |t|^2) -> sn_wv (v' out, s = W v', partial |s|^2) -> sn_scale (u', sigma, W_sn)
 //   h3d_spectral_norm_bwd  sn_dot (partial sum(G * W_sn)) -> sn_bwd (dW)
-#include "common.hpp"
+#include "device_helpers.hpp"
+
+using h3d::wave_sum;
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxParts = 1024;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 // block-wide sum of one value per thread (fixed order): returns the total to every thread
 __device__ __forceinline__ float block_sum(float v, float* red) {

@@ -21,12 +21,6 @@ constexpr int kRowsFwd = 128;     // pixels of one forward workgroup
 constexpr int kRowsBwd = 512;     // pixels of one backward workgroup = one row of the partial-sum buffers
 constexpr int kPlanes = 4;        // partial sums per sine channel: da * i, da * j, da * lab, da
 
-__device__ __forceinline__ float linspace_pm1(int n, int i) {   // torch.linspace(-1, 1, n)[i]
-    if (n == 1) return -1.f;
-    const float step = 2.f / (float)(n - 1);
-    return (i < n / 2) ? -1.f + step * (float)i : 1.f - step * (float)(n - 1 - i);
-}
-
 // The three coordinates of the workgroup's pixels r0 .. r0 + n - 1 of image b -> LDS (one entry per pixel, read by every
 // thread as a broadcast).  lab = seg / label_dim * 2 - 1 in this order, a true division; without a label map lab = 0.
 __device__ __forceinline__ void stage_coords(float* ci, float* cj, float* cl, const int64_t* __restrict__ seg, int b, int r0,

@@ -39,12 +39,6 @@ struct Args {
 
 __device__ __forceinline__ float lrelu(float v) { return fmaxf(v, 0.2f * v); }
 
-__device__ __forceinline__ float linspace_pm1(int n, int i) {   // torch.linspace(-1, 1, n)[i]
-    if (n == 1) return -1.f;
-    const float step = 2.f / (float)(n - 1);
-    return (i < n / 2) ? -1.f + step * (float)i : 1.f - step * (float)(n - 1 - i);
-}
-
 template <int NTW>
 __global__ __launch_bounds__(kFieldThreads) void synthesis_kernel(Args A) {
     extern __shared__ __attribute__((aligned(16))) float smem[];

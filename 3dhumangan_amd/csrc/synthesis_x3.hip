@@ -61,12 +61,6 @@ constexpr float kX2ActLimit = 32768.f;
 
 __device__ __forceinline__ float lrelu(float v) { return vmax(v, 0.2f * v); }
 
-__device__ __forceinline__ float linspace_pm1(int n, int i) {
-    if (n == 1) return -1.f;
-    const float step = 2.f / (float)(n - 1);
-    return (i < n / 2) ? -1.f + step * (float)i : 1.f - step * (float)(n - 1 - i);
-}
-
 // K order of every GEMM that consumes accumulators ("acc order", as in field_x3.hip): register r = 8j + e of accumulator
 // tile t IS element e of the lane's B fragment of k-step 2t + j, so fragments are assembled without any cross-lane move;
 // the host packs the K dimension of those weight matrices accordingly (pack_stream_bf16(acc_order=True)):

@@ -37,12 +37,6 @@ struct Args {
 
 __device__ __forceinline__ float lrelu(float v) { return vmax(v, 0.2f * v); }
 
-__device__ __forceinline__ float linspace_pm1(int n, int i) {   // torch.linspace(-1, 1, n)[i]
-    if (n == 1) return -1.f;
-    const float step = 2.f / (float)(n - 1);
-    return (i < n / 2) ? -1.f + step * (float)i : 1.f - step * (float)(n - 1 - i);
-}
-
 // Per-block view of the kernel state.  Rebuilt at the top of every block iteration from LAUNDERED copies of the weight /
 // table pointers, the wave's tile ids and the lane id: none of the per-phase fragment addresses is then loop-invariant
 // for the compiler, which would otherwise hoist the first k-steps' weight loads of every GEMM (and their addresses) out

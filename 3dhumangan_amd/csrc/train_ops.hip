@@ -5,8 +5,11 @@
 //                                        recomputes the cosine instead of keeping three intermediates alive.
 //   h3d_ray_integrate_bwd                gradient of lib/generators/volume_rendering.py:12-56 (ray_integration) w.r.t. the
 //                                        field tensor: one read of the field, one write of its gradient.
-#include "common.hpp"
+#include "composite.hpp"
+#include "device_helpers.hpp"
 #include <hip/hip_fp16.h>
+
+using namespace h3d;
 
 namespace {
 
@@ -144,20 +147,6 @@ __global__ __launch_bounds__(kThreads) void film_sin_bwd(const T* __restrict__ x
 //   2 (4 waves)  a_s = sum_c gO[c] * F[s][c]  (row s by wave s % 4; lanes stride the row 16 bytes at a time)
 //   3 (wave 0)   g_s = dL/dw_s, suffix sums, dL/dsigma_s -> LDS
 //   4 (4 waves)  dF[s][c] = w'_s * gO[c], dF[s][C] = dL/dsigma_s
-__device__ __forceinline__ float density_fn(float x, int clamp_mode) {
-    if (clamp_mode == 1) return x > 20.f ? x : log1pf(expf(x));
-    return fmaxf(x, 0.f);
-}
-__device__ __forceinline__ float density_deriv(float x, int clamp_mode) {
-    if (clamp_mode == 1) return x > 20.f ? 1.f : 1.f / (1.f + expf(-x));
-    return x > 0.f ? 1.f : 0.f;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 template <int V>
 __global__ __launch_bounds__(kThreads) void ray_integrate_bwd_kernel(
     const float* __restrict__ field, const float* __restrict__ z_vals, const float* __restrict__ noise,
@@ -183,28 +172,18 @@ __global__ __launch_bounds__(kThreads) void ray_integrate_bwd_kernel(
         for (int s0 = 0; s0 < S; s0 += 64) {
             const int s = s0 + lane;
             const bool ok = s < S;
-            float f = 1.f, alpha = 0.f, da = 0.f;
+            Sample sm;
+            float da = 0.f;
             if (ok) {
-                float sg = blk[(int64_t)s * W + C];
-                if (nz) sg += nz[s];
-                const float delta = (s == S - 1) ? 1e9f : z[s + 1] - z[s];
-                const float e = expf(-delta * density_fn(sg, clamp_mode));          // = 1 - alpha
-                alpha = 1.f - e;
-                f = (1.f - alpha) + 1e-12f;
-                da = delta * e * density_deriv(sg, clamp_mode);
+                sm = composite_sample(blk[(int64_t)s * W + C], z, nz, s, s == S - 1, clamp_mode);
+                da = composite_dalpha(sm, clamp_mode);
             }
-            float incl = f;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const float u = __shfl_up(incl, off, 64);
-                if (lane >= off) incl *= u;
-            }
-            float excl = __shfl_up(incl, 1, 64);
-            if (lane == 0) excl = 1.f;
+            const float incl = scan_inclusive<64>(sm.f, lane, 64);
+            const float excl = scan_exclusive<64>(incl, lane);
             const float T = carry * excl;
-            carry *= __shfl(incl, 63, 64);
-            if (ok) { w_s[s] = alpha * T; T_s[s] = T; f_s[s] = f; da_s[s] = da; }
-            wsum += alpha * T;
+            carry *= tile_product<64>(incl);
+            if (ok) { w_s[s] = sm.alpha * T; T_s[s] = T; f_s[s] = sm.f; da_s[s] = da; }
+            wsum += sm.alpha * T;
         }
         wsum = wave_sum(wsum);
         if (lane == 0) misc[0] = 1.f - wsum;
