@@ -158,6 +158,9 @@ _SIGNATURES = {
     "h3d_mesh_rasterize": (C.c_int, [_p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "h3d_upfirdn2d": (C.c_int, [_p, _p, _p, _i, _i, _i, _i, _i, C.POINTER(_l), _i, _i, _i, _i, C.POINTER(_l),
                                 _i, _i, _i, _i, _i, _i, _i, _f, _p]),
+    "h3d_smpl_shape": (C.c_int, [_p, _p, _p, _p, _i, _i, _i, _p]),
+    "h3d_smpl_pose": (C.c_int, [_p] * 9 + [_i, _i, _i, _i, _p]),
+    "h3d_smpl_skin": (C.c_int, [_p] * 8 + [_i, _i, _i, _p]),
 }
 
 

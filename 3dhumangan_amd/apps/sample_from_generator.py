@@ -7,7 +7,12 @@ absent) drives the generator with the procedural body of `synthetic.py`; with ra
 `--checkpoint`) it is a plumbing / throughput run.  `--smpl-record PATH.npz` drives it through the real front-end
 instead: one SMPL regression record (the keys preprocess_smpl_fix_body reads) with `joints_index`,
 `smpl_tpose_vertices`, `faces` and `faces_to_labels`; the camera preprocessor then rasterises the mesh on the device
-and the `_smpl` images are its semantics.
+and the `_smpl` images are its semantics.  `--pose-sequence PATH.npz` (poses [n,J,3] axis-angle, betas,
+optionally orig_cam [n,4]) with `--smpl-model PATH.npz` (the arrays of lib/components/smpl.SMPL plus faces,
+faces_to_labels, optionally joints_index) poses the body instead of turning the camera: all poses go through the SMPL
+forward and smpl_conditions on the device in one batch, and there is one frame per pose -- the camera fixed, or, with
+`--n_angles K` given as well, frame i at angle i mod K of the sweep.  `--pose-sequence synthetic` takes the procedural
+model and motion of `synthetic.py` (`--n_poses` frames) and needs no file.
 
     python -m 3dhumangan_amd.apps.sample_from_generator --config MAP3DBN --seeds 1 2 --n_angles 8 --save png
 """
@@ -60,13 +65,66 @@ def generate_frames(generator, preprocessor, config, seed, conditions, n_angles,
     pan, tilt = camera_sweep(n_angles, angle_range_h, angle_range_v, back_and_forth)
     frames, semantics = [], []
     for a_h, a_v in zip(pan.to(dev), tilt.to(dev)):
-        a_h, a_v = a_h.reshape(1, 1), a_v.reshape(1, 1)
-        view = preprocessor.forward_with_rotation(dict(base), a_h, a_v, torch.zeros_like(a_h), **config)
-        sem = view["rasterized_semantics"].clamp(-1, 1)
-        sem = torch.where((sem == 0).all(dim=1, keepdim=True), torch.ones_like(sem), sem)      # empty pixels -> white
+        frame, sem = _one_frame(generator, preprocessor, config, z, base, a_h, a_v)
         semantics.append(sem)
-        frames.append(generator.staged_forward(z, view, **config)["rgbs"].clamp(-1, 1))
+        frames.append(frame)
     return to_uint8_nhwc(torch.cat(frames).float()), to_uint8_nhwc(torch.cat(semantics).float())
+
+
+def _one_frame(generator, preprocessor, config, z, base, a_h, a_v):
+    """Batch-1 conditions at one camera angle -> (rgbs, semantics with empty pixels white), both clamped to [-1, 1]."""
+    a_h, a_v = a_h.reshape(1, 1), a_v.reshape(1, 1)
+    view = preprocessor.forward_with_rotation(dict(base), a_h, a_v, torch.zeros_like(a_h), **config)
+    sem = view["rasterized_semantics"].clamp(-1, 1)
+    sem = torch.where((sem == 0).all(dim=1, keepdim=True), torch.ones_like(sem), sem)      # empty pixels -> white
+    return generator.staged_forward(z, view, **config)["rgbs"].clamp(-1, 1), sem
+
+
+@torch.no_grad()
+def generate_pose_frames(generator, preprocessor, config, seed, conditions, pan, tilt):
+    """One frame per item of the batched `conditions` (one pose each) for the latent of `seed`; frame i is seen from
+    (pan[i % len(pan)], tilt[i % len(pan)]).  -> (frames, rasterized_semantics), both uint8 [n_poses,H,W,3].  The RNGs are seeded
+    anew for every frame, so each frame draws the same latent and the same ray jitter: two frames differ through their pose and
+    camera alone, and a repeated pose gives the same frame."""
+    dev = generator.device
+    pan, tilt = pan.to(dev), tilt.to(dev)
+    cached = getattr(generator, "cached_avg_latent", None)
+    if cached is not None and config.get("cache_avg_latent") and config.get("truncation_psi", 1.0) < 1.0 and cached() is None:
+        latent_for_seed(seed, config["latent_dim"])         # the truncation mean, drawn where the first frame of a sweep draws it,
+        generator.generate_avg_latent()                     # but ahead of the frames: no frame's jitter may depend on being first
+    frames, semantics = [], []
+    for i in range(conditions["scales"].shape[0]):
+        z = latent_for_seed(seed, config["latent_dim"]).to(dev)
+        base = {k: v[i:i + 1].to(dev) for k, v in conditions.items()}
+        frame, sem = _one_frame(generator, preprocessor, config, z, base, pan[i % len(pan)], tilt[i % len(pan)])
+        semantics.append(sem)
+        frames.append(frame)
+    return to_uint8_nhwc(torch.cat(frames).float()), to_uint8_nhwc(torch.cat(semantics).float())
+
+
+def load_pose_sequence(model_path, sequence_path, dev, n_synthetic=8):
+    """--smpl-model / --pose-sequence: -> (conditions of every pose of the sequence, batched on `dev`, a CameraPreprocessor on
+    `dev` with the model's faces and labels).  One SMPL forward and one smpl_conditions call for the whole sequence."""
+    from ..lib.components import smpl as smpl_ops
+    if sequence_path == "synthetic" and model_path is None:
+        model = synthetic.make_smpl_model()
+    elif model_path is None:
+        raise ValueError("--pose-sequence PATH.npz needs --smpl-model PATH.npz (only `--pose-sequence synthetic` brings its own)")
+    else:
+        model = dict(np.load(model_path))
+    n_joints = np.asarray(model["parents"]).reshape(-1).shape[0]
+    seq = synthetic.make_pose_sequence(n_synthetic) if sequence_path == "synthetic" else dict(np.load(sequence_path))
+    poses = torch.as_tensor(seq["poses"]).float().reshape(-1, n_joints, 3).to(dev)
+    n = poses.shape[0]
+    betas = torch.as_tensor(seq["betas"]).float().reshape(-1, np.asarray(model["shapedirs"]).shape[2]).to(dev)
+    cam = torch.as_tensor(seq["orig_cam"]).float().reshape(-1, 4) if "orig_cam" in seq else torch.tensor([[1.6, 1.6, 0.0, 0.0]])
+    body = smpl_ops.SMPL({k: model[k] for k in smpl_ops.MODEL_KEYS}, device=dev)
+    out = body.forward(betas, poses[:, 1:].reshape(n, -1), poses[:, 0])
+    joints_index = model["joints_index"].tolist() if "joints_index" in model else list(range(n_joints))
+    cond = lib_data.smpl_conditions(out, cam.expand(n, 4) if cam.shape[0] == 1 else cam, joints_index, model["v_template"])
+    pre = lib_data.CameraPreprocessor(dev)
+    pre.init_smpl(torch.as_tensor(model["faces"]), torch.as_tensor(model["faces_to_labels"]))
+    return cond, pre
 
 
 def load_smpl_record(path, dev):
@@ -111,14 +169,26 @@ def main(argv=None):
     ap.add_argument("--output_dir", type=str, default="results/sample_from_generator")
     ap.add_argument("--postfix", type=str, default="")
     ap.add_argument("--lock_view_dependence", default=None)
-    ap.add_argument("--n_angles", type=int, default=40)
+    ap.add_argument("--n_angles", type=int, default=None, help="camera angles of the sweep (default 40)")
     ap.add_argument("--back_and_forth", default=False, action="store_true")
     ap.add_argument("--save", type=str, default="png", choices=["mp4", "png", "gif"])
     ap.add_argument("--stitch", default=False, action="store_true")
     ap.add_argument("--synthetic-conditions", action="store_true", default=True)
     ap.add_argument("--smpl-record", type=str, default=None, help="an .npz SMPL record (+ joints_index, smpl_tpose_vertices, "
                     "faces, faces_to_labels): conditions and the _smpl images through the front-end and its rasteriser")
+    ap.add_argument("--smpl-model", type=str, default=None, help="an .npz SMPL model (v_template, shapedirs, posedirs, "
+                    "J_regressor, parents, lbs_weights, faces, faces_to_labels): the body that --pose-sequence poses")
+    ap.add_argument("--pose-sequence", type=str, default=None, help="an .npz pose sequence (poses [n,J,3], betas, orig_cam) or "
+                    "`synthetic`: one frame per pose; the camera is fixed unless --n_angles is given as well")
+    ap.add_argument("--n_poses", type=int, default=8, help="frames of the procedural motion of `--pose-sequence synthetic`")
     opt = ap.parse_args(argv)
+    sweep_given = opt.n_angles is not None
+    if opt.n_angles is None:
+        opt.n_angles = 40
+    if opt.smpl_model is not None and opt.pose_sequence is None:
+        raise ValueError("--smpl-model goes with --pose-sequence")
+    if opt.pose_sequence is not None and opt.smpl_record is not None:
+        raise ValueError("--pose-sequence and --smpl-record are two ways to give the body: pass one")
     if opt.dataroot is not None:
         raise NotImplementedError("the SHHQ dataset reader / SMPL preprocessor need licensed assets and pytorch3d; "
                                   "run with the synthetic conditions")
@@ -144,10 +214,16 @@ def main(argv=None):
     preprocessor = synthetic.SyntheticPreprocessor(device)
     if opt.smpl_record is not None:
         record, preprocessor = load_smpl_record(opt.smpl_record, device)
+    if opt.pose_sequence is not None:
+        sequence, preprocessor = load_pose_sequence(opt.smpl_model, opt.pose_sequence, device, opt.n_poses)
+        pan, tilt = camera_sweep(opt.n_angles, math.pi / 6, 0, opt.back_and_forth) if sweep_given else (torch.zeros(1), torch.zeros(1))
     for seed in opt.seeds:
-        data = record if opt.smpl_record is not None else synthetic.make_conditions(1, 6890, seed=seed)
-        frames, semantics = generate_frames(generator, preprocessor, config, seed, data, opt.n_angles, math.pi / 6, 0,
-                                            opt.back_and_forth)
+        if opt.pose_sequence is not None:
+            frames, semantics = generate_pose_frames(generator, preprocessor, config, seed, sequence, pan, tilt)
+        else:
+            data = record if opt.smpl_record is not None else synthetic.make_conditions(1, 6890, seed=seed)
+            frames, semantics = generate_frames(generator, preprocessor, config, seed, data, opt.n_angles, math.pi / 6, 0,
+                                                opt.back_and_forth)
         if opt.stitch:
             frames = np.stack([np.concatenate([f, s], axis=0) for f, s in zip(frames, semantics)])
         _save(os.path.join(out_dir, f"{seed:03d}_uncond"), frames, opt.save)

@@ -16,6 +16,7 @@ import math
 import torch
 
 from ..components import raster
+from ..components import smpl as smpl_ops
 
 FOV = math.pi * 12 / 180
 FOCAL = 1.0 / math.tan(FOV / 2)                      # 9.5144: intrinsics[0,0] of every sample
@@ -68,6 +69,59 @@ def preprocess_smpl_fix_body(pred, joints_index, smpl_tpose_vertices, inference=
     if inference:
         out["body_shape"] = f64(pred["betas"])[0].float()
     return out
+
+
+def smpl_conditions_math(fk_matrices, joints, full_pose, orig_cam, joints_index):
+    """The small matrices of preprocess_smpl_fix_body for a batch, in float64 on the inputs' device (plain torch, CPU or GPU):
+    fk_matrices [B,J,4,4], joints [B,Jall,3], full_pose [B,J,3,3], orig_cam [B,4] -> dict of float64 tensors scales [B],
+    intrinsics, T, cano_matrices [B,4,4], fk_matrices [B,J,4,4] (= cano . A), skeletons_xyz [B,len(joints_index),3]."""
+    dev = fk_matrices.device
+    B = fk_matrices.shape[0]
+    cam = orig_cam.reshape(B, -1)[:, :4].float().double()                                  # stored as float32
+    sx = cam[:, 0] / 2.0
+    K = torch.diag(torch.tensor([FOCAL, FOCAL, 1.0, 1.0], dtype=torch.float64, device=dev)).expand(B, 4, 4).clone()
+    T = torch.eye(4, dtype=torch.float64, device=dev).repeat(B, 1, 1)
+    T[:, 0, 3], T[:, 1, 3], T[:, 2, 3] = cam[:, 2], cam[:, 3], FOCAL / sx
+    rx_pi = torch.tensor([[1.0, 0, 0], [0, math.cos(math.pi), -math.sin(math.pi)], [0, math.sin(math.pi), math.cos(math.pi)]],
+                         dtype=torch.float64, device=dev)
+    cano = torch.eye(4, dtype=torch.float64, device=dev).repeat(B, 1, 1)
+    cano[:, :3, :3] = rx_pi @ torch.linalg.inv(full_pose[:, 0].double())                    # a true inverse, as the dataset code takes
+    fk = cano[:, None] @ fk_matrices.double()
+    sk = joints.float().double()[:, list(joints_index)]
+    sk = sk @ cano[:, :3, :3].transpose(1, 2) + cano[:, None, :3, 3]
+    return {"scales": sx, "intrinsics": K, "T": T, "cano_matrices": cano, "fk_matrices": fk, "skeletons_xyz": sk}
+
+
+@torch.no_grad()
+def smpl_conditions(smpl_out, orig_cam, joints_index, smpl_tpose_vertices):
+    """The batched, on-device counterpart of preprocess_smpl_fix_body: `smpl_out` is the dict of components.smpl.SMPL.forward
+    for B bodies (device tensors), orig_cam [B,4] (sx, sy, tx, ty), smpl_tpose_vertices [V,3] the model's template.  -> what
+    preprocess_smpl_fix_body returns per record, stacked over the batch (float32, on the device): scales [B], skeletons_xyz,
+    intrinsics, vertices, tpose_vertices, full_pose [B,J,3,3], fk_matrices, lbs_weights [B,V,J], cano_matrices, R, T.
+
+    The root rotation comes from smpl_out["full_pose"] when that holds matrices, else from global_orient / body_pose (axis-angle
+    goes through batch_rodrigues).  The vertices are the shaped template skinned with cano . A by the HIP skinning kernel -- no
+    pose offsets, as the dataset code applies none; the small matrices are float64 torch ops on the device."""
+    A = smpl_out["fk_matrices"]
+    B, J = A.shape[:2]
+    dev = A.device
+    pose = smpl_out.get("full_pose")
+    if pose is None or pose.shape[-2:] != (3, 3) or pose.dim() != 4:
+        go, bp = smpl_out["global_orient"], smpl_out["body_pose"]
+        if go.shape[-2:] == (3, 3) and go.dim() >= 3:
+            pose = torch.cat([go.reshape(B, -1, 3, 3), bp.reshape(B, -1, 3, 3)], dim=1)
+        else:
+            aa = torch.cat([go.reshape(B, -1), bp.reshape(B, -1)], dim=1).reshape(-1, 3)
+            pose = smpl_ops.batch_rodrigues(aa.float()).view(B, J, 3, 3)
+    pose = pose.to(dev)
+    m = smpl_conditions_math(A, smpl_out["joints"], pose, torch.as_tensor(orig_cam).to(dev), joints_index)
+    vertices = smpl_ops.skin_vertices(smpl_out["tpose_vertices"], A, smpl_out["lbs_weights"], rigid=m["cano_matrices"].float())
+    template = torch.as_tensor(smpl_tpose_vertices).float().to(dev).clone()
+    template[..., 1] += 0.35
+    return {"scales": m["scales"].float(), "skeletons_xyz": m["skeletons_xyz"].float(), "intrinsics": m["intrinsics"].float(),
+            "vertices": vertices, "tpose_vertices": template[None].repeat(B, 1, 1), "full_pose": pose.float(),
+            "fk_matrices": m["fk_matrices"].float(), "lbs_weights": smpl_out["lbs_weights"].float()[None].repeat(B, 1, 1),
+            "cano_matrices": m["cano_matrices"].float(), "R": torch.eye(4, device=dev).repeat(B, 1, 1), "T": m["T"].float()}
 
 
 def raster_translation(data):

@@ -243,6 +243,46 @@ def make_mesh_conditions(batch, seed=0, pose_scale=0.5, scale=0.8):
     return cond, faces, labels
 
 
+def make_smpl_model(seed=0, num_betas=10):
+    """A procedural SMPL-shaped body model on the tube_body mesh, what lib/components/smpl.SMPL is built from (and what
+    `--smpl-model` of the sample app loads from an .npz): v_template [V,3], parents [24], lbs_weights [V,24], a sparse convex
+    J_regressor [24,V] (each joint is the softmax-weighted mean of its 32 nearest vertices, rows sum to 1 -- so the regressed
+    joints sit near, not on, the tube's rest joints), small seeded shapedirs [V,3,num_betas] (smooth in space: centimetres per
+    unit beta) and posedirs [207, 3V] (millimetres), plus faces, faces_to_labels and joints_index for the front-end.  A dict
+    of numpy arrays."""
+    J, V, W, faces, labels = tube_body()
+    n, g = V.shape[0], torch.Generator().manual_seed(3000 + seed)
+    near = torch.topk(torch.cdist(J, V).square(), 32, dim=1, largest=False)
+    reg = torch.zeros(24, n)
+    reg.scatter_(1, near.indices, torch.softmax(-near.values / 0.005, dim=1))
+    # shape directions: low-frequency fields of the rest position, so that neighbouring vertices move together
+    freq = torch.randn(num_betas, 3, 3, generator=g) * 2.0
+    phase = torch.rand(num_betas, 3, generator=g) * 2 * math.pi
+    shapedirs = 0.02 * torch.sin(torch.einsum("lkc,vc->vkl", freq, V) + phase.T[None])
+    posedirs = 0.002 * torch.randn(23 * 9, n * 3, generator=g)
+    return {"v_template": V.numpy(), "shapedirs": shapedirs.contiguous().numpy(), "posedirs": posedirs.numpy(),
+            "J_regressor": reg.numpy(), "parents": torch.tensor(PARENTS).numpy(), "lbs_weights": W.numpy(),
+            "faces": faces.numpy(), "faces_to_labels": labels.numpy(), "joints_index": torch.arange(24).numpy()}
+
+
+def make_pose_sequence(n, seed=0, num_betas=10, pose_scale=0.5, scale=0.8):
+    """A smooth seeded motion of `n` frames for a 24-joint body: poses [n,24,3] axis-angle (every joint swings sinusoidally about
+    a seeded axis with a seeded amplitude <= pose_scale, period and phase; the root stays upright), betas [1,num_betas] and
+    orig_cam [n,4] (the weak-perspective camera of make_conditions) -- the arrays `--pose-sequence` of the sample app loads from
+    an .npz.  Frames with equal time (n = 1 aside, frame i sits at t = i / n) are equal."""
+    g = torch.Generator().manual_seed(4000 + seed)
+    axis = torch.randn(24, 3, generator=g)
+    axis = axis / axis.norm(dim=-1, keepdim=True)
+    amp = torch.rand(24, 1, generator=g) * pose_scale
+    cycles = torch.randint(1, 3, (24, 1), generator=g).float()
+    phase = torch.rand(24, 1, generator=g) * 2 * math.pi
+    t = torch.arange(n).float()[:, None, None] / max(n, 1)
+    poses = axis[None] * amp[None] * torch.sin(2 * math.pi * cycles[None] * t + phase[None])
+    poses[:, 0] = 0
+    cam = torch.tensor([[2 * scale, 2 * scale, 0.0, 0.0]]).repeat(n, 1)
+    return {"poses": poses.contiguous().numpy(), "betas": (0.5 * torch.randn(1, num_betas, generator=g)).numpy(), "orig_cam": cam.numpy()}
+
+
 def make_smpl_record(seed=0, pose_scale=0.5, scale=0.8):
     """One SMPL regression record of the shape lib/data/conditions.preprocess_smpl_fix_body reads, on the tube_body mesh, plus
     the assets the front-end needs beside it (joints_index, smpl_tpose_vertices, faces, faces_to_labels): a dict of numpy

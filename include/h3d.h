@@ -896,6 +896,27 @@ int h3d_mesh_rasterize(const float* vertices, const int32_t* faces, const float*
                        int64_t* segments, float* semantics, void* workspace, int B, int V, int F, int H, int W,
                        h3d_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * SMPL forward == lbs() of the reference (lib/components/smpl.py:11-107) with the smplx helpers it calls, fp32, B bodies at once.
+ * Three launches; no atomics, fixed summation order: bit-identical between runs, and an item's result does not depend on its batch.
+ *   h3d_smpl_shape   v_shaped [B,V,3] = v_template [V,3] + shapedirs [V,3,NB] . betas [B,NB]            (NB = 0: betas may be NULL)
+ *   h3d_smpl_pose    one wave per item.  joint_template [J,3] = J_regressor . v_template and joint_dirs [J,3,NB] = J_regressor .
+ *                    shapedirs are folded by the caller (the joints are linear in betas).  pose: [B,J,3] axis-angle (pose2rot = 1,
+ *                    smplx's batch_rodrigues: angle = |aa + 1e-8|) or [B,J,3,3] matrices (pose2rot = 0).  parents [J] int32 with
+ *                    parents[0] = -1, 0 <= parents[i] < i (the caller validates).  Writes A [B,J,4,4] (rest -> posed transforms, 16-byte
+ *                    aligned), joints [B,J,3], joints_posed [B,J,3] and pose_feature [B,(J-1)*9] = R[1:] - I (NULL allowed at J = 1).
+ *   h3d_smpl_skin    verts [B,V,3] = sum_j W[v,j] (rigid_b .) A_bj . [v_in + pose_feature_b . posedirs, 1]  (+ transl_b).
+ *                    v_in [B,V,3]; posedirs [(J-1)*9, 3V] with pose_feature, or both NULL: no pose offsets; rigid [B,4,4] (rows 0..2
+ *                    used) and transl [B,3] optional; lbs_weights [V,J].  posedirs is read once per tile of 8 items.
+ * 1 <= J <= 64, V >= 1, NB >= 0, 1 <= B <= 524280. */
+int h3d_smpl_shape(const float* betas, const float* v_template, const float* shapedirs, float* v_shaped, int B, int V, int NB,
+                   h3d_stream_t stream);
+int h3d_smpl_pose(const float* betas, const float* pose, const float* joint_template, const float* joint_dirs,
+                  const int32_t* parents, float* A, float* joints, float* joints_posed, float* pose_feature, int B, int J, int NB,
+                  int pose2rot, h3d_stream_t stream);
+int h3d_smpl_skin(const float* v_in, const float* pose_feature, const float* posedirs, const float* A, const float* rigid,
+                  const float* transl, const float* lbs_weights, float* verts, int B, int V, int J, h3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
