@@ -161,6 +161,10 @@ _SIGNATURES = {
     "h3d_smpl_shape": (C.c_int, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "h3d_smpl_pose": (C.c_int, [_p] * 9 + [_i, _i, _i, _i, _p]),
     "h3d_smpl_skin": (C.c_int, [_p] * 8 + [_i, _i, _i, _p]),
+    "h3d_seg_loss_rows": (C.c_int, []),
+    "h3d_seg_histogram": (C.c_int, [_p, _p, _p, _p, _p, _l, _i, _p]),
+    "h3d_seg_loss_fwd": (C.c_int, [_p, C.POINTER(_l), _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "h3d_seg_loss_bwd": (C.c_int, [_p, C.POINTER(_l), _p, _p, _p, _p, _f, _p, C.POINTER(_l), _i, _i, _i, _i, _i, _p]),
 }
 
 

@@ -15,8 +15,14 @@ nn.Module class under `torch.nn.modules`; dotted names (`torch` + `os.system`), 
 `copyreg._reconstructor` and everything else raise `UnpicklingError`.  This narrows what a file can name to constructors of
 data containers; it is a hardening of a pickle loader, not a sandbox -- prefer the `*_state_dict.pth` files (which go
 through torch's `weights_only=True` loader and never reach this unpickler) for files of unknown origin.
+
+Writing: save_training_state / load_training_state keep the reference's file NAMES ({step:08d}_generator.pth, ...) so that a run
+directory looks the same, but hold state dicts only -- the reference pickles whole modules under its own class paths, which this
+package must not imitate.  The optimizer and scaler files are what the reference writes (state_dict()); the EMA is a dict of its
+attributes; {step:08d}_trainer.pth (step, epoch, seed) is new and written LAST, so a step counts as saved once it exists.
 """
 import io
+import os
 import pickle
 
 import torch
@@ -136,12 +142,15 @@ def state_dict_of(obj):
 
 
 def load_generator(generator, path, ema_path=None, map_location="cpu", strict=True):
-    """Load generator weights from any of the reference's formats into `generator` (this build's Map3DGenerator):
-    `path` a state-dict file or a pickled module; `ema_path` (optional) a pickled ExponentialMovingAverage whose shadow
+    """Load generator weights from any of the reference's formats, or from the files save_training_state writes, into `generator`
+    (this build's Map3DGenerator): `path` a state-dict file or a pickled module; `ema_path` (optional) a pickled
+    ExponentialMovingAverage, or the dict of its attributes, whose shadow
     parameters are then copied over the trainable parameters -- what the reference's apps evaluate with."""
     generator.load_state_dict(state_dict_of(load_reference_pickle(path, map_location)), strict=strict)
     if ema_path is not None:
         ema = load_reference_pickle(ema_path, map_location)
+        if isinstance(ema, dict) and "shadow_params" in ema:            # written by save_training_state
+            ema = ema_from_state(ema)
         if not isinstance(ema, ExponentialMovingAverage):
             raise TypeError(f"{ema_path} does not hold an ExponentialMovingAverage")
         live = [p for p in generator.parameters() if p.requires_grad]
@@ -149,3 +158,90 @@ def load_generator(generator, path, ema_path=None, map_location="cpu", strict=Tr
             raise ValueError("EMA shadow list does not match the generator's parameters (count / shapes / order)")
         ema.copy_to(generator.parameters())
     return generator
+
+
+# ---------------------------------------------------------------------------------------------------------- training state
+TRAINING_FILES = ("generator", "discriminator", "ema", "optimizer_G", "optimizer_D", "scaler", "trainer")
+
+
+def ema_state(ema):
+    """the attributes of an ExponentialMovingAverage as plain data (loads through torch's weights_only loader)"""
+    return {"decay": float(ema.decay), "num_updates": ema.num_updates, "shadow_params": [p.detach().clone() for p in ema.shadow_params]}
+
+
+def ema_from_state(state, device=None):
+    ema = ExponentialMovingAverage([], decay=float(state["decay"]), use_num_updates=state["num_updates"] is not None)
+    ema.num_updates = state["num_updates"]
+    ema.shadow_params = [p.detach().clone() if device is None else p.detach().to(device) for p in state["shadow_params"]]
+    return ema
+
+
+def _step_of(name):
+    return int(name[:8]) if name.endswith(".pth") and name[:8].isdigit() and name[8:9] == "_" else None
+
+
+def saved_steps(directory):
+    """steps with a complete set of files in `directory` (the trainer file is written last), ascending"""
+    if not os.path.isdir(directory):
+        return []
+    return sorted(_step_of(n) for n in os.listdir(directory) if n.endswith("_trainer.pth") and _step_of(n) is not None)
+
+
+def prune_training_state(directory, keep_interval):
+    """base_trainer.py:186-189: remove the .pth files whose step is not a multiple of `keep_interval` -> the removed names"""
+    removed = []
+    for name in sorted(os.listdir(directory)):
+        step = _step_of(name)
+        if step is not None and step % keep_interval != 0:
+            os.remove(os.path.join(directory, name))
+            removed.append(name)
+    return removed
+
+
+def save_training_state(directory, step, generator, discriminator, ema, optimizer_G, optimizer_D, scaler=None, epoch=0, seed=0,
+                        keep_interval=None):
+    """Write {step:08d}_{generator, discriminator, ema, optimizer_G, optimizer_D[, scaler], trainer}.pth into `directory` (file
+    names of base_trainer.py:183-202).  ``keep_interval``: first remove earlier files as the reference does before it saves."""
+    os.makedirs(directory, exist_ok=True)
+    if keep_interval:
+        prune_training_state(directory, keep_interval)
+    parts = {"generator": generator.state_dict(), "discriminator": discriminator.state_dict(), "ema": ema_state(ema),
+             "optimizer_G": optimizer_G.state_dict(), "optimizer_D": optimizer_D.state_dict()}
+    if scaler is not None:
+        parts["scaler"] = scaler.state_dict()
+    parts["trainer"] = {"step": int(step), "epoch": int(epoch), "seed": int(seed)}          # last: marks the set complete
+    for kind, obj in parts.items():
+        path = os.path.join(directory, f"{int(step):08d}_{kind}.pth")
+        torch.save(obj, path + ".tmp")
+        os.replace(path + ".tmp", path)
+    return [f"{int(step):08d}_{kind}.pth" for kind in parts]
+
+
+def load_training_state(directory, generator, discriminator, ema, optimizer_G, optimizer_D, scaler=None, step=None,
+                        map_location="cpu"):
+    """Restore what save_training_state wrote, from the newest complete step of `directory` (or `step`), in place -> the
+    trainer record {step, epoch, seed}.  `ema`'s attributes are overwritten; its shadow tensors land on the device of the
+    generator's parameters.  Raises FileNotFoundError when the directory holds no complete step."""
+    steps = saved_steps(directory)
+    if step is None:
+        if not steps:
+            raise FileNotFoundError(f"no saved training state in {directory}")
+        step = steps[-1]
+    elif step not in steps:
+        raise FileNotFoundError(f"no complete training state of step {step} in {directory}")
+
+    def read(kind):
+        return torch.load(os.path.join(directory, f"{int(step):08d}_{kind}.pth"), map_location=map_location, weights_only=True)
+
+    generator.load_state_dict(read("generator"), strict=True)
+    discriminator.load_state_dict(read("discriminator"), strict=True)
+    device = next((p.device for p in generator.parameters()), torch.device("cpu"))
+    restored = ema_from_state(read("ema"), device)
+    if len(restored.shadow_params) != len(ema.shadow_params):
+        raise ValueError("saved EMA shadow list does not match the generator's parameters")
+    ema.decay, ema.num_updates, ema.shadow_params = restored.decay, restored.num_updates, restored.shadow_params
+    optimizer_G.load_state_dict(read("optimizer_G"))
+    optimizer_D.load_state_dict(read("optimizer_D"))
+    if scaler is not None:
+        scaler.load_state_dict(read("scaler"))
+    return read("trainer")

@@ -34,7 +34,7 @@ def _stepped_since_update(scaler, optimizer):
 
 
 def discriminator_step(D, optimizer, real_images, fake_images, gt_segments, meta, do_r1=True, r1_mode="reference",
-                       distributed=False, grad_clip=None, amp_dtype=None, scaler=None, update_scaler=False):
+                       distributed=False, grad_clip=None, amp_dtype=None, scaler=None, update_scaler=False, seg_loss=None):
     """-> dict of detached scalars.  meta: gan_lambda, segmentation_lambda, r1_lambda, label_dim (config keys).
 
     ``r1_mode``: "reference" (default, drop-in) is the reference's penalty -- the channel norms of sample 0 of the shard
@@ -49,7 +49,11 @@ def discriminator_step(D, optimizer, real_images, fake_images, gt_segments, meta
     calls scaler.step -- so ``update_scaler`` is off by default here.  (Changed in round 3: the defaults used to be
     r1_mode="per_sample" and an update per D step.)  A caller that runs D steps ALONE, or several per G step, never reaches
     that update: the step notices that this optimizer was already stepped since the scaler's last update (GradScaler would
-    raise on the second unscale_) and updates the scale itself first."""
+    raise on the second unscale_) and updates the scale itself first.
+
+    ``seg_loss``: the segmentation-loss function, called as losses.segmentation_loss is (None: that one, plain torch);
+    losses.segmentation_loss_fused runs it on the HIP op.  meta["segmentation_loss_mode"] (default "cross_entropy_balanced")
+    is passed through."""
     if scaler is not None and _stepped_since_update(scaler, optimizer):
         scaler.update()
     amp = dict(device_type="cuda", dtype=amp_dtype or torch.float16, enabled=amp_dtype is not None)
@@ -82,9 +86,11 @@ def discriminator_step(D, optimizer, real_images, fake_images, gt_segments, meta
         penalty = torch.where(torch.isnan(penalty), torch.zeros_like(penalty), penalty)   # the reference's NaN guard (:291)
     seg = real.new_zeros(())
     if seg_lambda > 0 and out_real["segments"].shape[1] > 0:
-        s_real, acc, _ = losses.segmentation_loss(out_real["segments"], gt_segments, meta["label_dim"], meta.get("segmentation_weights"))
-        s_gen, _, _ = losses.segmentation_loss(out_fake["segments"], torch.zeros_like(gt_segments), meta["label_dim"],
-                                               meta.get("segmentation_weights"))
+        seg_fn = losses.segmentation_loss if seg_loss is None else seg_loss
+        seg_mode = meta.get("segmentation_loss_mode", "cross_entropy_balanced")
+        s_real, acc, _ = seg_fn(out_real["segments"], gt_segments, meta["label_dim"], meta.get("segmentation_weights"), seg_mode)
+        s_gen, _, _ = seg_fn(out_fake["segments"], torch.zeros_like(gt_segments), meta["label_dim"],
+                             meta.get("segmentation_weights"), seg_mode)
         seg = (s_real + s_gen) * seg_lambda
     loss = gan + 4 * penalty + seg                       # lazy regularisation factor of the reference (:392)
     total = gan + 4 * r1_scale * penalty + seg

@@ -62,7 +62,7 @@ G_STEP_D_GRADS = os.environ.get("H3D_G_STEP_D_GRADS", "0") == "1"
 
 def generator_step(G, D, optimizer, z, conditions, meta, gt_segments=None, ema=None, distributed=False, d_step_count=0,
                    gen_modal="rgbs", latent_indices=None, generator_kwargs=None, amp_dtype=None, scaler=None,
-                   update_scaler=True, d_param_grads=None):
+                   update_scaler=True, d_param_grads=None, seg_loss=None):
     """-> dict of detached scalars.  meta: the config dict (gan_lambda, segmentation_lambda, label_dim, grad_clip and every
     forward key of the generator).  ``gt_segments`` [B,H,W] int64 (the rasterised body-part labels of the conditions) feeds
     the segmentation term; the unconditional phase of the reference (latent_lambda = perceptual = photometric = 0 in every
@@ -70,7 +70,10 @@ def generator_step(G, D, optimizer, z, conditions, meta, gt_segments=None, ema=N
 
     ``amp_dtype`` (torch.float16 / torch.bfloat16) runs both networks under autocast -- the reference's AMP mode
     (base_trainer.py:50-51, torch.cuda.amp.autocast + GradScaler): the library GEMMs and convolutions run in that type, the
-    HIP kernels between them compute in fp32; pass a torch.amp.GradScaler as ``scaler`` for float16."""
+    HIP kernels between them compute in fp32; pass a torch.amp.GradScaler as ``scaler`` for float16.
+
+    ``seg_loss``: the segmentation-loss function (None: losses.segmentation_loss, plain torch; losses.segmentation_loss_fused:
+    the HIP op); meta["segmentation_loss_mode"] is passed through."""
     gan_lambda, seg_lambda = meta.get("gan_lambda", 0), meta.get("segmentation_lambda", 0)
     optimizer.zero_grad(set_to_none=True)
     fwd = {k: v for k, v in meta.items() if isinstance(k, str)}
@@ -81,14 +84,15 @@ def generator_step(G, D, optimizer, z, conditions, meta, gt_segments=None, ema=N
         p.requires_grad_(False)
     try:
         return _generator_step(G, D, optimizer, z, conditions, meta, gt_segments, ema, distributed, d_step_count, gen_modal, fwd,
-                               gan_lambda, seg_lambda, amp_dtype, scaler, update_scaler)
+                               gan_lambda, seg_lambda, amp_dtype, scaler, update_scaler,
+                               losses.segmentation_loss if seg_loss is None else seg_loss)
     finally:
         for p in frozen:
             p.requires_grad_(True)
 
 
 def _generator_step(G, D, optimizer, z, conditions, meta, gt_segments, ema, distributed, d_step_count, gen_modal, fwd, gan_lambda,
-                    seg_lambda, amp_dtype, scaler, update_scaler):
+                    seg_lambda, amp_dtype, scaler, update_scaler, seg_fn):
     with torch.autocast("cuda", dtype=amp_dtype or torch.float16, enabled=amp_dtype is not None):
         out = G(z, conditions, **fwd)
         d_out = D(out[gen_modal], conditions, 1.0)
@@ -99,8 +103,8 @@ def _generator_step(G, D, optimizer, z, conditions, meta, gt_segments, ema, dist
         seg = pred.new_zeros(())
         if "segments" in d_out and d_out["segments"].shape[1] > 0:
             if seg_lambda > 0 and gt_segments is not None:
-                seg = losses.segmentation_loss(d_out["segments"].float(), gt_segments, meta["label_dim"],
-                                               meta.get("segmentation_weights"))[0] * seg_lambda
+                seg = seg_fn(d_out["segments"].float(), gt_segments, meta["label_dim"], meta.get("segmentation_weights"),
+                             meta.get("segmentation_loss_mode", "cross_entropy_balanced"))[0] * seg_lambda
             else:
                 seg = d_out["segments"].sum() * 0
         latent = d_out["latents"].sum() * 0 if "latents" in d_out else 0.0

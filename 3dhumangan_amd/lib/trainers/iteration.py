@@ -17,9 +17,10 @@ from .g_step import generator_step
 
 def adversarial_iteration(G, D, opt_d, opt_g, z, conditions, real_images, gt_segments, meta, generator_kwargs=None, ema=None,
                           distributed=False, grad_clip=None, amp_dtype=None, scaler=None, r1_mode="reference", do_r1=True,
-                          on_phase=None):
+                          on_phase=None, seg_loss=None):
     """-> (discriminator-step scalars, generator-step scalars).  ``on_phase(name)`` is called before the D step ("d"), between
-    the steps ("g") and at the end ("end"): the bench records its HIP events there."""
+    the steps ("g") and at the end ("end"): the bench records its HIP events there.  ``seg_loss``: handed to both steps (None:
+    losses.segmentation_loss)."""
     mark = on_phase or (lambda name: None)
     fwd = {k: v for k, v in meta.items() if isinstance(k, str)}
     fwd.update(generator_kwargs or {})
@@ -27,9 +28,9 @@ def adversarial_iteration(G, D, opt_d, opt_g, z, conditions, real_images, gt_seg
     with torch.no_grad(), torch.autocast("cuda", dtype=amp_dtype or torch.float16, enabled=amp_dtype is not None):
         fake = G(z, conditions, **fwd)["rgbs"].float()
     d = discriminator_step(D, opt_d, real_images, fake, gt_segments, meta, do_r1=do_r1, r1_mode=r1_mode, distributed=distributed,
-                           grad_clip=grad_clip, amp_dtype=amp_dtype, scaler=scaler)
+                           grad_clip=grad_clip, amp_dtype=amp_dtype, scaler=scaler, seg_loss=seg_loss)
     mark("g")
     g = generator_step(G, D, opt_g, z, conditions, meta, gt_segments=gt_segments, ema=ema, distributed=distributed,
-                       generator_kwargs=generator_kwargs, amp_dtype=amp_dtype, scaler=scaler)
+                       generator_kwargs=generator_kwargs, amp_dtype=amp_dtype, scaler=scaler, seg_loss=seg_loss)
     mark("end")
     return d, g

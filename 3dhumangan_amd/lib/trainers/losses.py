@@ -50,16 +50,26 @@ def r1_penalty(grad, r1_lambda, mode="per_sample"):
     return 0.5 * r1_lambda * r1_statistic(grad, mode).mean()
 
 
-def segmentation_loss(segments, gt_segments, label_dim, prior_weights=None):
-    """Class-balanced cross entropy of the discriminator's segmentation head (phase_trainer.py:204-256, mode
-    "cross_entropy_balanced") -> (loss, accuracy over the foreground classes, mean foreground probability)."""
+SEGMENTATION_LOSS_MODES = ("cross_entropy", "cross_entropy_balanced", "cross_entropy_multiclass", "softplus")
+
+
+def segmentation_loss(segments, gt_segments, label_dim, prior_weights=None, mode="cross_entropy_balanced"):
+    """Loss of the discriminator's segmentation head (phase_trainer.py:204-256) in plain torch, the four segmentation_loss_mode
+    values; the default is the class-balanced cross entropy -> (loss, accuracy over the foreground classes, mean foreground
+    probability).  The CPU path, and the parity yardstick of segmentation_loss_fused."""
+    if mode not in SEGMENTATION_LOSS_MODES:
+        raise ValueError(f"unknown segmentation_loss_mode {mode!r} (one of {SEGMENTATION_LOSS_MODES})")
+    if mode == "softplus" and label_dim < 3:
+        raise ValueError("segmentation_loss_mode 'softplus' needs label_dim >= 3 (channel groups {0}, {1}, {2..})")
     B, _, H, W = segments.shape
     if gt_segments.shape[1] != H or gt_segments.shape[2] != W:
         gt_segments = F.interpolate(gt_segments.unsqueeze(1).float(), (H, W), mode="nearest").squeeze(1).long()
     pw = torch.ones(label_dim, dtype=segments.dtype, device=segments.device) if prior_weights is None else \
         torch.as_tensor(prior_weights, dtype=segments.dtype, device=segments.device)
     pw = pw / pw.mean()
-    if torch.any(gt_segments > 0):
+    if mode != "cross_entropy_balanced":
+        loss = _segmentation_loss_other(segments, gt_segments, label_dim, mode)
+    elif torch.any(gt_segments > 0):
         one_hot = F.one_hot(gt_segments, num_classes=label_dim).permute(0, 3, 1, 2)
         occ = one_hot.sum(dim=(0, 2, 3))
         occ[0] = 0
@@ -73,3 +83,21 @@ def segmentation_loss(segments, gt_segments, label_dim, prior_weights=None):
     real_prob = (1 - torch.softmax(segments, dim=1)[:, 0]).mean()
     accuracy = ((torch.argmax(segments[:, 1:], dim=1) + 1) == gt_segments).float().mean()
     return loss, accuracy, real_prob
+
+
+def _segmentation_loss_other(segments, gt_segments, label_dim, mode):
+    """the three modes no shipped config selects (phase_trainer.py:222-227, 243-250)"""
+    if mode == "cross_entropy":
+        return F.cross_entropy(segments, gt_segments)
+    one_hot = F.one_hot(gt_segments, num_classes=label_dim).permute(0, 3, 1, 2).clone()
+    one_hot[:, 1][gt_segments > 0] = 1                  # channel 1 is "any foreground"
+    if mode == "cross_entropy_multiclass":
+        return F.binary_cross_entropy_with_logits(segments, one_hot.to(segments.dtype))
+    flipped = torch.where(one_hot > 0, -segments, segments)
+    return (F.softplus(flipped[:, 0]).mean() + F.softplus(flipped[:, 1]).mean() + F.softplus(flipped[:, 2:]).mean()) / 3
+
+
+def segmentation_loss_fused(segments, gt_segments, label_dim, prior_weights=None, mode="cross_entropy_balanced"):
+    """segmentation_loss on the fused HIP op (lib/components/ops/seg_loss.py): same arguments, same triple; ROCm tensors only."""
+    from ..components.ops import seg_loss as seg_ops
+    return seg_ops.seg_loss(segments, gt_segments, label_dim, prior_weights, mode)

@@ -295,3 +295,43 @@ def make_smpl_record(seed=0, pose_scale=0.5, scale=0.8):
             "fk_matrices": A[None].numpy(), "lbs_weights": W.numpy(), "betas": torch.zeros(1, 10).numpy(),
             "joints_index": torch.arange(24).numpy(), "smpl_tpose_vertices": V.numpy(), "faces": faces.numpy(),
             "faces_to_labels": labels.numpy()}
+
+
+class SyntheticTrainingSource:
+    """A learnable toy task that needs no assets, in the trainer's data-source protocol (lib/trainers/phase_trainer.py):
+    `length` posed tube bodies (make_mesh_conditions); the "photograph" of a body is a fixed palette applied to its UNROTATED
+    rasterisation plus a little seeded noise, and `body_segments` is that rasterisation.
+
+        batches(batch, step, device) -> dict: images [B,3,H,W] in [-1, 1], body_segments [B,H,W] int64, indices [B] and the
+                                              condition entries CameraPreprocessor and the generator read
+        faces [F,3], faces_to_labels [F]      the topology CameraPreprocessor.init_smpl takes
+    Item i of step s is (s * batch + i) % length.  The rasterisation runs on the device (HIP), once per item and size."""
+
+    def __init__(self, length=8, gen_height=256, gen_width=128, seed=0, noise=0.02, label_dim=26):
+        self.length, self.size, self.seed, self.noise = int(length), (int(gen_height), int(gen_width)), int(seed), float(noise)
+        self.conditions, self.faces, self.faces_to_labels = make_mesh_conditions(self.length, seed=seed)
+        g = torch.Generator().manual_seed(4000 + seed)
+        self.palette = torch.rand(label_dim + 2, 3, generator=g) * 2 - 1
+        self.palette[:2] = 1.0                                               # labels 0 / 1: the white background
+        self._cache = {}
+
+    def _rasterised(self, device):
+        key = str(device)
+        if key not in self._cache:
+            pre = SyntheticPreprocessor(device)
+            pre.init_smpl(self.faces, self.faces_to_labels)
+            cond = {k: v.to(device) for k, v in self.conditions.items()}
+            zero = torch.zeros(self.length)
+            seg = pre.forward_with_rotation(cond, zero, zero, zero, gen_height=self.size[0], gen_width=self.size[1])["rasterized_segments"]
+            self._cache[key] = (cond, seg.long(), self.palette.to(device)[seg.long().clamp(0, self.palette.shape[0] - 1)].permute(0, 3, 1, 2))
+        return self._cache[key]
+
+    def batches(self, batch, step, device):
+        cond, seg, rgb = self._rasterised(device)
+        idx = (torch.arange(batch) + int(step) * batch) % self.length
+        g = torch.Generator().manual_seed(self.seed * 7919 + int(step))
+        noise = (torch.randn(batch, 3, *self.size, generator=g) * self.noise).to(device)
+        idx_d = idx.to(device)
+        out = {k: v[idx_d].contiguous() for k, v in cond.items()}
+        out.update(images=(rgb[idx_d] + noise).clamp(-1, 1).contiguous(), body_segments=seg[idx_d].contiguous(), indices=idx_d)
+        return out

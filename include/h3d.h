@@ -917,6 +917,38 @@ int h3d_smpl_pose(const float* betas, const float* pose, const float* joint_temp
 int h3d_smpl_skin(const float* v_in, const float* pose_feature, const float* posedirs, const float* A, const float* rigid,
                   const float* transl, const float* lbs_weights, float* verts, int B, int V, int J, h3d_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Segmentation loss of the discriminator's label head == PhaseTrainer._calculate_segmentation_loss (lib/trainers/phase_trainer.py:
+ * 203-256), fused: the logits are read once forward and once backward.  No atomics; per-workgroup partials whose fp64 sum over the
+ * rows (h3d_rows_sum_f64) is the result: bit-identical between runs.
+ *   x [B,L,H,W] fp32 logits with ELEMENT strides x_strides[4] = {batch, channel, row, column} (>= 0); 2 <= L <= 64;
+ *   labels [B,H,W] int64 dense, values in [0, L) (precondition; outside it the result is undefined, nothing is indexed
+ *          out of bounds: kind 0 gives such a pixel no loss and no gradient, kinds 1 and 2 treat it as foreground of no class).
+ *   kind 0: softmax cross entropy, pixel n weighted by coef[labels[n]] (coef [L] fp32, NULL: weight 1) -- the modes "cross_entropy"
+ *           and "cross_entropy_balanced";  kind 1: BCE with logits against the one-hot with channel 1 also set where the label is
+ *           > 0 ("cross_entropy_multiclass");  kind 2: softplus of the sign-flipped logits, channel groups {0}, {1}, {2..} ("softplus",
+ *           L >= 3).
+ * Strides with channel stride 1 and ONE pixel pitch >= L for the whole tensor (a channel slice of a channels-last tensor) are staged
+ * through LDS, a tile of 256 pixels per workgroup; every other layout is read by its strides (contiguous NCHW: coalesced).
+ *   h3d_seg_loss_rows   pixels per partial row R: every partial below has ceil(B*H*W / R) rows
+ *   h3d_seg_histogram   labels [N] -> partial [rows, L] int32 (scratch) -> occ [L] int64 (NULL allowed) and coef [L] fp32 (NULL
+ *                       allowed), the coefficients of "cross_entropy_balanced": 0 for class 0 and absent classes, else
+ *                       N / (occ[c] * n_present) * prior[c] (prior [L] fp32 normalised to mean 1, NULL: 1); all 1 when no label is
+ *                       above 0 (the reference's plain-cross-entropy branch, selected on the device).  Two launches.
+ *   h3d_seg_loss_fwd    partial [rows, 4] fp32 = {sum of the per-pixel loss terms, pixels whose first argmax over channels >= 1 equals
+ *                       the label, sum of 1 - softmax[0], 0}; stats [B*H*W, 2] fp32 = {max, 1 / sum exp(x - max)} per pixel (what
+ *                       kind 0's backward reads; NULL allowed).  loss = sum[0] / N (kind 0), / (N L) (kind 1), / (3 N) (kind 2).
+ *   h3d_seg_loss_bwd    dx [B,L,H,W] with element strides dx_strides[4] = grad_out[0] * scale * d(sum[0]) / dx; grad_out: DEVICE
+ *                       scalar, scale: the mode's 1 / count.  Staged when x is, and dx is dense channels-last. */
+int h3d_seg_loss_rows(void);
+int h3d_seg_histogram(const int64_t* labels, int32_t* partial, int64_t* occ, const float* prior, float* coef, int64_t N, int L,
+                      h3d_stream_t stream);
+int h3d_seg_loss_fwd(const float* x, const int64_t* x_strides, const int64_t* labels, const float* coef, float* partial, float* stats,
+                     int B, int H, int W, int L, int kind, h3d_stream_t stream);
+int h3d_seg_loss_bwd(const float* x, const int64_t* x_strides, const int64_t* labels, const float* coef, const float* stats,
+                     const float* grad_out, float scale, float* dx, const int64_t* dx_strides, int B, int H, int W, int L, int kind,
+                     h3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
