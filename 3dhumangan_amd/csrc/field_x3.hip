@@ -26,6 +26,13 @@
 //   fused A6    the feature head is evaluated with the operands swapped (rows = samples), so the weighted sum over
 //               the samples of a ray is a sum over accumulator registers; compositing weights come from a
 //               segmented 32-lane product scan (S = 8..32: 32/S rays per wave step; S = 64, 128: carry).
+//   ray head    fused launches with feature_dim == hidden_dim and S >= 32 (every shipped config; template parameter RAYHEAD):
+//               head and compositing are both linear, so the head runs once per RAY.  The colour layer is the step's last
+//               GEMM and runs sample-major; its sine, the three colour heads (a halving butterfly over the lanes) and the
+//               compositing of h = film_colour(X) run in fp32 VALU; hbar = sum_s w_s h_s is parked in the ray's feature slots
+//               and every 32 rays the wave multiplies its parked rows by Wf, fragments read straight from the blob (the
+//               per-step weight stream ends before W_FEAT): 6 instead of 7 GEMMs per step.  Everything else -- S < 32,
+//               feature_dim != hidden_dim, the unfused field -- keeps the per-sample head above.
 //
 // X2 variant (template parameter, h3d_neural_field_x2 / h3d_render_fused_x2): the hidden-layer contractions (FiLM 0-3, the
 // hidden part of the colour layer, the feature head) run in the "x2" arithmetic of x3_common.hpp -- one f16 product + one
@@ -137,6 +144,7 @@ struct Args {
 };
 
 constexpr int kHeadPad = 64;       // bytes behind every head's fragment rows in LDS (bank staggering)
+constexpr int kRayInfo = 96;       // RAYHEAD: floats per wave of the ray table ([32] sum of w, [32] background term, [32] unit index or -1)
 constexpr int kJointRows = 40;     // GEOIN: LDS table of 3 + 24 + 13 float4 rows (joints at rows 3..26, zeros around them)
 
 // two fp32 activations -> packed f16 hi halves (returned) and packed f16 lo halves, plain (non-packed) VALU only:
@@ -330,18 +338,54 @@ __device__ __forceinline__ void input_layer(f32x16 (&dst)[NT], const half8 (&ih)
 }
 
 
-constexpr int kRingX2 = 8;                      // x2: one more buffer, the refill lags one stage (WeightRing LAG = 1)
+// RAYHEAD: value of lane (l ^ K) of the same 32-lane half (ds_swizzle in bit mode: no address register)
+template <int K>
+__device__ __forceinline__ float swz_xor(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), (K << 10) | 0x1f));
+}
 
-template <int NT, bool FUSED, bool X2, bool GEOIN = false>
+// RAYHEAD: sixteen running sums materialised in vector registers at this point of the program (two statements: an asm takes at
+// most 30 operands, and a read-write one counts twice)
+__device__ __forceinline__ void pin_rows(float (&v)[16]) {
+    asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
+    asm volatile("" : "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]));
+}
+
+// One step of the halving (reduce-scatter) butterfly over lane bit K: of the N rows the lane still holds it keeps the upper
+// (bit set) or lower half and adds the partner's sums of those rows -- N / 2 exchanges per colour instead of N.
+template <int K, int N>
+__device__ __forceinline__ void halve_rows(float (&lg)[3][16], bool bit) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int i = 0; i < N / 2; ++i) {
+            const float keep = bit ? lg[c][i + N / 2] : lg[c][i];
+            const float send = bit ? lg[c][i] : lg[c][i + N / 2];
+            lg[c][i] = keep + swz_xor<K>(send);
+        }
+}
+
+constexpr int kRingX2 = 8;                     // x2: one more buffer, the refill lags one stage (WeightRing LAG = 1)
+
+// RAYHEAD (fused launches with F == Hd and S >= 32, i.e. one ray per wave unit): the feature head is linear and so is the
+// compositing, so   sum_s w_s (inv Wf h_s + b_f) + back  =  inv Wf (sum_s w_s h_s) + b_f sum_s w_s + back,   h_s = film_colour(X_s).
+// The colour layer runs sample-major (SWAP), its sine and the three colour heads run in fp32 VALU on that layout, the
+// compositing weights are applied to h itself, and the ray's hbar = sum_s w_s h_s (Hd floats) is parked in the ray's feature slots.
+// Every 32 rays (and once more behind the unit-group loop) the wave runs the head ONCE on its own <= 32 parked rows: one SWAP
+// GEMM against the W_FEAT stages read straight from the blob -- 1/S of the per-sample head's matrix work, and the per-step
+// weight stream ends before W_FEAT.
+template <int NT, bool FUSED, bool X2, bool GEOIN = false, bool RAYHEAD = false>
 __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
+    static_assert(!RAYHEAD || FUSED, "the per-ray head belongs to the fused render");
     constexpr int KS = 2 * NT;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const LayoutX3& L = A.L;
     const int HdP = L.HdP;
     float* tab0 = smem;                                 // [ST_COUNT][2][HdP]  A1 / A0 per step
-    float* tfeat0 = tab0 + ST_COUNT * 2 * HdP;          // [HdP] feature-head bias
-    float* scratch = tfeat0 + HdP;                      // [4 waves][64]: compositing weights, background terms
-    float* joint0 = scratch + 4 * 64;                   // GEOIN: [kJointRows] float4 (x, y, z, 0): joints at rows 3 .. 26
+    float* tfeat0 = tab0 + ST_COUNT * 2 * HdP;          // [HdP] feature-head bias; RAYHEAD: [3][HdP] fp32 rows of the colour heads
+    float* scratch = tfeat0 + (RAYHEAD ? 3 : 1) * HdP;  // [4 waves][64]: compositing weights, background terms
+    float* rayinfo0 = scratch + 4 * 64;                 // RAYHEAD: [4 waves][kRayInfo]: sum of w, background, unit of the rays since the last flush
+    float* joint0 = rayinfo0 + (RAYHEAD ? 4 * kRayInfo : 0);      // GEOIN: [kJointRows] float4 (x, y, z, 0): joints at rows 3 .. 26
     unsigned char* head0 = reinterpret_cast<unsigned char*>(joint0 + (GEOIN ? kJointRows * 4 : 0));      // head A-fragment rows
     unsigned char* ring_lds = head0 + 4 * ((X2 ? 3 : 2) * KS * 32 + kHeadPad);           // [ring depth][NT*2 KB]
 
@@ -389,7 +433,20 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
             q[0] = a1;
             q[2] = a0;
         }
-        for (int idx = t; idx < HdP; idx += 256) tfeat0[idx] = idx < F ? bf[idx] : 0.f;
+        if constexpr (RAYHEAD) {
+            // colour-head rows in fp32 by channel, (hi + lo) * head_inv, from the A-fragment planes [head][plane][KS][half][8]
+            const _Float16* __restrict__ hw = reinterpret_cast<const _Float16*>(blob + L.head_w);
+            const float* __restrict__ hinv = reinterpret_cast<const float*>(blob + L.head_inv);
+            constexpr int plane = KS * 16;
+            for (int idx = t; idx < 3 * plane; idx += 256) {
+                const int c = idx / plane, u = idx - c * plane;
+                const _Float16* q = hw + (c + 1) * L.head_planes * plane + u;
+                tfeat0[c * plane + acc_k(u >> 4, (u >> 3) & 1, u & 7)] = ((float)q[0] + (float)q[plane]) * hinv[c + 1];
+            }
+            (void)bf;
+        } else {
+            for (int idx = t; idx < HdP; idx += 256) tfeat0[idx] = idx < F ? bf[idx] : 0.f;
+        }
         if constexpr (GEOIN) {
             if (t < kJointRows * 4) {
                 const int row = t >> 2, c = t & 3, j = row - 3;
@@ -419,7 +476,7 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
     const int seglen = FUSED ? (S < 32 ? S : 32) : 32;
     typedef typename std::conditional<X2, WeightRing<NT, kRingX2, 1>, WeightRing<NT>>::type Ring;
     Ring ring;
-    ring.init(A.blob + L.w[0], ring_lds, L.stages, wave, lane);
+    ring.init(A.blob + L.w[0], ring_lds, RAYHEAD ? L.stages - KS : L.stages, wave, lane);      // RAYHEAD: the stream ends before W_FEAT
     int n_groups = A.n_groups;
     if constexpr (FUSED) {
         if (A.ref_mode == 2) n_groups = (ref_units + 3) >> 2;
@@ -449,6 +506,7 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
 
     // Persistent workgroups: the sample's tables above are built once, then the workgroup walks the unit groups blockIdx.x,
     // blockIdx.x + gridDim.x, .. with the weight ring running across them (the stream wraps at the end of every step).
+    int nray = 0;                 // RAYHEAD: rays this wave has parked since its last flush (the same in all four waves)
 #pragma unroll 1
     for (int ug = blockIdx.x; ug < n_groups; ug += gridDim.x) {
     int64_t uidx = (int64_t)ug * 4 + wave;                  // this wave's unit
@@ -469,6 +527,7 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
     float rayacc[NT];
 #pragma unroll
     for (int i = 0; i < NT; ++i) rayacc[i] = 0.f;
+    float rgbacc1 = 0.f, wacc = 0.f;      // RAYHEAD: second colour sum of the lane (rayacc = this lane half's part of hbar), sum of w
 
     f32x16 X[NT], Y[NT];          // the two accumulator sets
 
@@ -596,7 +655,9 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
             }
             split8(v, kSA, xh[KS], xl[KS]);
         }
-        layer<NT, KS + 1, true, false, true, X2>(X, xh, xl, b6, ring, p_f3, p_col, hacc, head_lds, lane);
+        // (RAYHEAD: sample-major, X[row = sample][lane = channel]; mm<T, SWAP> only swaps the operands, the same stages serve)
+        if constexpr (RAYHEAD) layer<NT, KS + 1, true, true, true, X2>(X, xh, xl, b6, ring, p_f3, none, hacc, head_lds, lane);
+        else layer<NT, KS + 1, true, false, true, X2>(X, xh, xl, b6, ring, p_f3, p_col, hacc, head_lds, lane);
         pin_agpr<NT>(X);
         // density of this lane's sample: head row 0 = accumulator register 0 of the lower lane half
         const float sigma = __shfl(hacc[0], m, 64) * hi0 + hb0;
@@ -636,6 +697,93 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
             }
         }
 
+        if constexpr (RAYHEAD) {
+            // ---- colour epilogue, colour heads and compositing in fp32 on the sample-major accumulators: register r of tile nt is
+            //      row (sample) (r >> 2) * 8 + 4 h + (r & 3), channel nt * 32 + m
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            // opaque copies of the lane indices: what is derived from them is computed here, not hoisted out of the unit-group loop
+            int me = m, he = h;
+            asm volatile("" : "+v"(me), "+v"(he));
+            float wr[16], wsum[4];
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) {
+                const f32x4 w4 = ld4(wl_lds + rg * 8 + 4 * he);
+                wr[rg * 4 + 0] = w4.x; wr[rg * 4 + 1] = w4.y; wr[rg * 4 + 2] = w4.z; wr[rg * 4 + 3] = w4.w;
+                wsum[rg] = (w4.x + w4.y) + (w4.z + w4.w);
+            }
+            float wtot = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+            wtot += __shfl_xor(wtot, 32, 64);
+            wacc += wtot;
+            const lds_ptr tcol = lane_base(tab + ST_COLOR * 2 * HdP, ((me >> 1) * 4 + (me & 1)) * 4);      // A1 of channel m; A0 8 bytes on
+            const lds_ptr thd = lane_base(tfeat, me * 4);
+            float lg[3][16];
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const float a1 = lds_ld<float>(tcol + nt * 256), a0 = lds_ld<float>(tcol + nt * 256 + 8);
+                const float q0 = lds_ld<float>(thd + nt * 128), q1 = lds_ld<float>(thd + (NT * 32 + nt * 32) * 4),
+                            q2 = lds_ld<float>(thd + (2 * NT * 32 + nt * 32) * 4);
+                pin1(X[nt]);
+                float s = 0.f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float hv = __builtin_amdgcn_sinf(fmaf(X[nt][r], a1, a0));
+                    lg[0][r] = nt == 0 ? q0 * hv : fmaf(q0, hv, lg[0][r]);
+                    lg[1][r] = nt == 0 ? q1 * hv : fmaf(q1, hv, lg[1][r]);
+                    lg[2][r] = nt == 0 ? q2 * hv : fmaf(q2, hv, lg[2][r]);
+                    s = r == 0 ? hv * wr[0] : fmaf(hv, wr[r], s);
+                }
+                rayacc[nt] += s;
+                // tile by tile: the sums are materialised here, in front of the next tile's pin1 (asm statements keep their order) --
+                // left to itself instruction selection starts every tile's sines first and holds all 128 of them
+                pin_rows(lg[0]); pin_rows(lg[1]); pin_rows(lg[2]);
+                asm volatile("" : "+v"(rayacc[nt]));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            // colour logits: sums over the 32 lanes of each half, as a halving butterfly -- the lane ends with the one row
+            // r = (m >> 1) & 15 of its half, both lanes of a pair with the same sums
+            halve_rows<16, 16>(lg, (me & 16) != 0);
+            halve_rows<8, 8>(lg, (me & 8) != 0);
+            halve_rows<4, 4>(lg, (me & 4) != 0);
+            halve_rows<2, 2>(lg, (me & 2) != 0);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) lg[c][0] += swz_xor<1>(lg[c][0]);
+            {
+                const int r = (me >> 1) & 15;
+                const float wrow = wl_lds[(r >> 2) * 8 + 4 * he + (r & 3)];
+                // even lanes: red and green of their row; odd lanes: blue
+                const bool odd = (me & 1) != 0;
+                float va = wrow / (1.f + expf(-(odd ? lg[2][0] + hb3 : lg[0][0] + hb1)));
+                float vb = odd ? 0.f : wrow / (1.f + expf(-(lg[1][0] + hb2)));
+                va += swz_xor<2>(va); vb += swz_xor<2>(vb);
+                va += swz_xor<4>(va); vb += swz_xor<4>(vb);
+                va += swz_xor<8>(va); vb += swz_xor<8>(vb);
+                va += swz_xor<16>(va); vb += swz_xor<16>(vb);
+                va += __shfl_xor(va, 32, 64); vb += __shfl_xor(vb, 32, 64);
+                rgbacc += va;
+                rgbacc1 += vb;
+            }
+            if (last_step) {
+                const int C = F + 3;
+                const bool live = n0 < N;
+                const float back = A.white_back ? wl_lds[32] : 0.f;
+                gf fray = a_feats + unit_ray * C;
+                if (live && lane == 0) { fray[0] = rgbacc + back; fray[1] = rgbacc1 + back; }
+                if (live && lane == 1) fray[2] = rgbacc + back;
+                // hbar = sum_s w_s h_s: parked in the ray's feature slots until the wave's next flush
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const float tot = rayacc[nt] + __shfl_xor(rayacc[nt], 32, 64);
+                    if (live && he == 0 && nt * 32 + me < F) fray[3 + nt * 32 + me] = tot;
+                }
+                if (lane == 0) {
+                    float* ri = rayinfo0 + wave * kRayInfo + nray;
+                    ri[0] = wacc;
+                    ri[32] = back;
+                    reinterpret_cast<int*>(ri)[64] = live ? (int)uidx : -1;
+                }
+            }
+        } else {
         // ---- feature head, sample-major accumulator: Y = film_color(X)^T * Wf^T  (+ colour heads on film_color(X))
         layer<NT, KS, true, true, true, X2>(Y, xh, xl, b6, ring, p_col, none, hacc, head_lds, lane);
         pin_agpr<NT>(Y);
@@ -747,26 +895,140 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
             }
             __builtin_amdgcn_wave_barrier();
         }
+        }   // per-sample head
+    }
+    if constexpr (RAYHEAD) {
+        // ---- deferred feature head: after 32 rays, and on the workgroup's last trip, the wave runs Wf once over its parked rows.
+        //      The four waves get here on the same trips (uniform control flow around the ring); the flush itself uses no barrier.
+        ++nray;
+        if (nray == 32 || n_groups - ug <= (int)gridDim.x) {
+            // the wave's own hbar stores have reached the L2, and the reloads below do not hit stale lines of the vector cache
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            __builtin_amdgcn_wave_barrier();
+            typedef const __attribute__((address_space(1))) unsigned char* gcb;
+            int mf = m, hf = h, lf = lane;          // opaque copies (see the colour epilogue)
+            asm volatile("" : "+v"(mf), "+v"(hf), "+v"(lf));
+            const int C = F + 3;
+            int opaque = 0;
+            asm volatile("" : "+s"(opaque));
+            const float* ri = rayinfo0 + opaque + wave * kRayInfo;
+            // A fragments: row m of the tile = ray number m since the last flush (rows without a ray: zeros)
+            const int my_unit = mf < nray ? reinterpret_cast<const int*>(ri)[64 + mf] : -1;
+            gcf hrow = a_feats + ((int64_t)b * A.R + (my_unit < 0 ? 0 : my_unit)) * C + 3;
+            gcb wf = (gcb)A.blob + L.w[W_FEAT] + lf * 16;
+            asm volatile("" : "+v"(wf));
+            const half8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+            zero_acc1(Y);
+            pin_agpr<NT>(Y);                               // the head's accumulators stay in the AGPR half, like the layers'
+#pragma unroll 1
+            for (int T = 0; T < NT; ++T) {                 // K-tile = two k-steps, in the stream's (accumulator) K order
+                half8 fh[2], fl[2];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    float v[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const int ch = 32 * T + 16 * j + 4 * hf + (e & 3) + 8 * (e >> 2);       // acc_k(2 T + j, h, e)
+                        v[e] = (my_unit >= 0 && ch < Hd) ? hrow[ch < Hd ? ch : 0] : 0.f;
+                    }
+                    split8(v, kSA, fh[j], fl[j]);
+                }
+                i32x8 rec;
+                if constexpr (X2) rec = x2_record(zero8, zero8, fh[0], fh[1]);      // the W_lo x_hi cross term only: W_hi x_lo runs in f16 below
+                gcb wt = wf + (int64_t)T * (2 * NT * 2048);
+                // weight fragments straight from the blob, four tiles at a time: all loads of a batch first, then its matrix
+                // instructions (one memory round trip per batch, not one per fragment)
+                constexpr int TB = 4;
+                typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+                typedef const __attribute__((address_space(1))) u32x4* g128;
+                static_for<0, NT / TB>([&](auto bc) __attribute__((always_inline)) {
+                    constexpr int t0 = decltype(bc)::value * TB;
+                    u32x4 bh[TB][2], bl[TB][2];                 // bl: the f16 lo fragment (x3) / the record's dwords 0-3 (x2, even stage only)
+                    u32x2 c1[TB];
+                    unsigned sc[TB];
+#pragma unroll
+                    for (int i = 0; i < TB; ++i) {
+                        gcb ev = wt + (t0 + i) * 2048, od = wt + (NT + t0 + i) * 2048;
+                        bh[i][0] = *reinterpret_cast<g128>(ev);
+                        bh[i][1] = *reinterpret_cast<g128>(od);
+                        bl[i][0] = *reinterpret_cast<g128>(ev + 1024);
+                        if constexpr (X2) {
+                            // the K-tile's fp6 weight record (pack_x2_unit): dwords 0-3 in the even stage, 4-5 and the scale dense in the odd one
+                            gcb dense = od + 1024 - lf * 16;
+                            c1[i] = *reinterpret_cast<const __attribute__((address_space(1))) u32x2*>(dense + lf * 8);
+                            sc[i] = *reinterpret_cast<const __attribute__((address_space(1))) unsigned*>(dense + 512 + lf * 4);
+                        } else {
+                            bl[i][1] = *reinterpret_cast<g128>(od + 1024);
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int i = 0; i < TB; ++i) {
+                        f32x16& acc = Y[t0 + i];
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            const half8 wh = __builtin_bit_cast(half8, bh[i][j]);
+                            acc = F16::mfma(fh[j], wh, acc);
+                            acc = F16::mfma(fl[j], wh, acc);
+                            if constexpr (!X2) acc = F16::mfma(fh[j], __builtin_bit_cast(half8, bl[i][j]), acc);
+                        }
+                        if constexpr (X2) {
+                            const i32x8 w6 = {(int)bl[i][0][0], (int)bl[i][0][1], (int)bl[i][0][2], (int)bl[i][0][3],
+                                              (int)c1[i][0], (int)c1[i][1], (int)sc[i], 0};
+                            acc = mm6<true>(w6, rec, acc);
+                        }
+                        pin1(acc);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+            }
+            // rows back over the parked ones: acc * inv_f + b_f * sum(w) + back
+            const __attribute__((address_space(1))) float* bfeat =
+                reinterpret_cast<const __attribute__((address_space(1))) float*>((gcb)A.blob + L.b_feat);
+            pin_agpr<NT>(Y);
+            float bfv[NT];
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) bfv[nt] = nt * 32 + mf < F ? bfeat[nt * 32 + mf] : 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = (r >> 2) * 8 + 4 * hf + (r & 3);
+                const float sw = ri[row], back = ri[32 + row];
+                const int ru = reinterpret_cast<const int*>(ri)[64 + row];
+                const bool okr = row < nray && ru >= 0;
+                gf fo = a_feats + ((int64_t)b * A.R + (okr ? ru : 0)) * C + 3 + mf;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+                    if (okr && nt * 32 + mf < F) fo[nt * 32] = fmaf(Y[nt][r], inv_f, fmaf(bfv[nt], sw, back));
+            }
+            __builtin_amdgcn_wave_barrier();
+            nray = 0;
+        }
     }
     }   // unit groups
     ring.drain();
 }
 
-size_t lds_bytes(const LayoutX3& L, bool geoin = false) {
-    return sizeof(float) * ((size_t)ST_COUNT * 2 * L.HdP + L.HdP + 4 * 64 + (geoin ? kJointRows * 4 : 0)) +
+size_t lds_bytes(const LayoutX3& L, bool geoin = false, bool rayhead = false) {
+    return sizeof(float) * ((size_t)ST_COUNT * 2 * L.HdP + (rayhead ? 3 * L.HdP + 4 * kRayInfo : L.HdP) + 4 * 64 + (geoin ? kJointRows * 4 : 0)) +
            (size_t)4 * (L.head_planes * L.KS * 32 + kHeadPad) + (L.head_planes == 3 ? kRingX2 : kWeightRingDepth) * (size_t)L.NT * 2048;
 }
 
-template <int NT, bool FUSED, bool X2, bool GEOIN = false>
+template <int NT, bool FUSED, bool X2, bool GEOIN = false, bool RAYHEAD = false>
 int launch_one(Args A, int B, int64_t groups, hipStream_t st) {
-    H3D_ALLOW_MAX_LDS((field_x3_kernel<NT, FUSED, X2, GEOIN>));
+    if constexpr (FUSED && !RAYHEAD) {
+        // one ray per wave unit and a head as wide as the hidden layer (every shipped config): the feature head runs once per ray
+        if (A.F == A.Hd && A.S >= 32) return launch_one<NT, FUSED, X2, GEOIN, true>(A, B, groups, st);
+    }
+    H3D_ALLOW_MAX_LDS((field_x3_kernel<NT, FUSED, X2, GEOIN, RAYHEAD>));
     A.n_groups = (int)groups;
     // about four persistent workgroups per CU in total (one resident per CU: registers): tables once per many unit groups, short tail
     int64_t per_sample = h3d::persistent_wgs(groups, B, 4);
     // refinement launch: a handful of listed units per batch item (workgroups beyond the list leave at once)
     if (A.ref_mode == 2) per_sample = std::max<int64_t>(1, std::min<int64_t>((A.ref_cap + 3) / 4, 8));
     h3d::pre_launch();
-    hipLaunchKernelGGL((field_x3_kernel<NT, FUSED, X2, GEOIN>), dim3((unsigned)per_sample, (unsigned)B), dim3(256), lds_bytes(A.L, GEOIN), st, A);
+    hipLaunchKernelGGL((field_x3_kernel<NT, FUSED, X2, GEOIN, RAYHEAD>), dim3((unsigned)per_sample, (unsigned)B), dim3(256),
+                       lds_bytes(A.L, GEOIN, RAYHEAD), st, A);
     return h3d::launch_status(FUSED ? (X2 ? "h3d_render_fused_x2" : "h3d_render_fused_x3") : (X2 ? "h3d_neural_field_x2" : "h3d_neural_field_x3"));
 }
 
