@@ -3,7 +3,9 @@ png / gif (mp4 when imageio is installed).  Same CLI flags, same config override
 convention (:26-29), angle schedule (:35-43), uint8 conversion (:59-62) and output naming (:140-149).
 
 The SMPL model file and the SHHQ dataset cannot ship, so `--synthetic-conditions` (the default when --dataroot is
-absent) drives the generator with the procedural body of `synthetic.py`; with random-init weights (no
+absent) drives the generator with the procedural body of `synthetic.py`; `--dataroot DIR --smpl-model PATH.npz` takes each
+seed's body from the records of a dataset in the reference's layout (lib/data/datasets.py), as the reference's app does: the items
+come in a shuffled order drawn before the first seed is set, the k-th seed takes the k-th of them; with random-init weights (no
 `--checkpoint`) it is a plumbing / throughput run.  `--smpl-record PATH.npz` drives it through the real front-end
 instead: one SMPL regression record (the keys preprocess_smpl_fix_body reads) with `joints_index`,
 `smpl_tpose_vertices`, `faces` and `faces_to_labels`; the camera preprocessor then rasterises the mesh on the device
@@ -185,13 +187,12 @@ def main(argv=None):
     sweep_given = opt.n_angles is not None
     if opt.n_angles is None:
         opt.n_angles = 40
-    if opt.smpl_model is not None and opt.pose_sequence is None:
-        raise ValueError("--smpl-model goes with --pose-sequence")
-    if opt.pose_sequence is not None and opt.smpl_record is not None:
-        raise ValueError("--pose-sequence and --smpl-record are two ways to give the body: pass one")
-    if opt.dataroot is not None:
-        raise NotImplementedError("the SHHQ dataset reader / SMPL preprocessor need licensed assets and pytorch3d; "
-                                  "run with the synthetic conditions")
+    if opt.smpl_model is not None and opt.pose_sequence is None and opt.dataroot is None:
+        raise ValueError("--smpl-model goes with --pose-sequence or --dataroot")
+    if sum(x is not None for x in (opt.pose_sequence, opt.smpl_record, opt.dataroot)) > 1:
+        raise ValueError("--pose-sequence, --smpl-record and --dataroot are three ways to give the body: pass one")
+    if opt.dataroot is not None and opt.smpl_model is None:
+        raise ValueError("--dataroot needs --smpl-model PATH.npz: the SMPL model as plain arrays (the licensed file cannot ship)")
     config = configs.get_config(opt)
     config = {k: v for k, v in config.items() if type(k) is str}
     config["truncation_psi"] = 0.7
@@ -214,14 +215,23 @@ def main(argv=None):
     preprocessor = synthetic.SyntheticPreprocessor(device)
     if opt.smpl_record is not None:
         record, preprocessor = load_smpl_record(opt.smpl_record, device)
+    if opt.dataroot is not None:
+        dataset = lib_data.SHHQDataset(**dict(config, dataroot=opt.dataroot, smpl_model=opt.smpl_model, inference=True, condition_only=True))
+        preprocessor = lib_data.get_preprocessor(device, opt.smpl_model)
+        order = torch.randperm(len(dataset)).tolist()       # the reference's shuffled loader, batch 1: drawn before any seed is set
     if opt.pose_sequence is not None:
         sequence, preprocessor = load_pose_sequence(opt.smpl_model, opt.pose_sequence, device, opt.n_poses)
         pan, tilt = camera_sweep(opt.n_angles, math.pi / 6, 0, opt.back_and_forth) if sweep_given else (torch.zeros(1), torch.zeros(1))
-    for seed in opt.seeds:
+    for k, seed in enumerate(opt.seeds):
         if opt.pose_sequence is not None:
             frames, semantics = generate_pose_frames(generator, preprocessor, config, seed, sequence, pan, tilt)
         else:
-            data = record if opt.smpl_record is not None else synthetic.make_conditions(1, 6890, seed=seed)
+            if opt.dataroot is not None:
+                item = dataset[order[k % len(order)]]
+                data = {k: v[None] for k, v in item.items()}
+                data["scales"] = data["scales"].reshape(1)
+            else:
+                data = record if opt.smpl_record is not None else synthetic.make_conditions(1, 6890, seed=seed)
             frames, semantics = generate_frames(generator, preprocessor, config, seed, data, opt.n_angles, math.pi / 6, 0,
                                                 opt.back_and_forth)
         if opt.stitch:

@@ -19,7 +19,8 @@ phase whose gen_modal != "rgbs", ada_interval != 0, dual_discrimination.
 
 Data source protocol: source.batches(batch, step, device) -> dict with images [B,3,H,W], body_segments [B,H,W] and the condition
 entries CameraPreprocessor and the generator read; source.faces, source.faces_to_labels; source.length.  The rank-r shard of
-step s is batches(batch, s * world_size + r, device).  synthetic.SyntheticTrainingSource is one; a dataset reader plugs in here.
+step s is batches(batch, s * world_size + r, device).  synthetic.SyntheticTrainingSource is one; lib/data/source.DatasetTrainingSource
+(a dataset in the reference's layout) is the other.
 """
 import json
 import os

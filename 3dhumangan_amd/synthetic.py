@@ -335,3 +335,43 @@ class SyntheticTrainingSource:
         out = {k: v[idx_d].contiguous() for k, v in cond.items()}
         out.update(images=(rgb[idx_d] + noise).clamp(-1, 1).contiguous(), body_segments=seg[idx_d].contiguous(), indices=idx_d)
         return out
+
+
+RECORD_ASSETS = ("joints_index", "smpl_tpose_vertices", "faces", "faces_to_labels")
+
+
+def write_example_dataset(root, length=8, height=64, width=32, seed=0, records="npz"):
+    """Write a procedural dataset of `length` items in the layout lib/data/datasets.SHHQDataset reads (CPU only, no licensed
+    asset): images/ (seeded smooth colours), masks/ (an ellipse, 255 inside), body_seg/ (label bands 0..24 inside the ellipse, as a
+    3-channel PNG whose channel 0 counts), inversions/*.npy (seeded latents [512]), smpl/ (make_smpl_record's records without the
+    assets, as plain-array .npz, or joblib .pkl with records="pkl") and smpl_model.npz (make_smpl_model).  -> root."""
+    import os
+
+    import numpy as np
+    from PIL import Image
+    if records not in ("npz", "pkl"):
+        raise ValueError(f"records must be 'npz' or 'pkl', got {records!r}")
+    for d in ("images", "masks", "body_seg", "inversions", "smpl"):
+        os.makedirs(os.path.join(root, d), exist_ok=True)
+    np.savez(os.path.join(root, "smpl_model.npz"), **make_smpl_model(seed))
+    yy, xx = np.meshgrid(np.linspace(-1, 1, height), np.linspace(-1, 1, width), indexing="ij")
+    for i in range(length):
+        rng = np.random.default_rng(seed * 100_003 + i)
+        name = f"{i + 1:06d}"
+        freq, phase = rng.uniform(0.5, 3.0, (3, 2)), rng.uniform(0, 2 * math.pi, 3)
+        rgb = np.stack([0.5 + 0.5 * np.sin(freq[c, 0] * yy * math.pi + freq[c, 1] * xx * math.pi + phase[c]) for c in range(3)], -1)
+        cy, cx, ry, rx = rng.uniform(-0.1, 0.1), rng.uniform(-0.1, 0.1), rng.uniform(0.6, 0.9), rng.uniform(0.5, 0.8)
+        inside = ((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 <= 1
+        band = np.clip(((yy - cy + ry) / (2 * ry) * 25).astype(np.int64), 0, 24)
+        seg = np.where(inside, band, 0).astype(np.uint8)
+        Image.fromarray((rgb * 255).round().astype(np.uint8)).save(os.path.join(root, "images", name + ".png"))
+        Image.fromarray(np.where(inside, 255, 0).astype(np.uint8)).save(os.path.join(root, "masks", name + ".png"))
+        Image.fromarray(np.stack([seg, seg, seg], -1)).save(os.path.join(root, "body_seg", name + ".png"))
+        np.save(os.path.join(root, "inversions", name + ".npy"), rng.standard_normal(512).astype(np.float32))
+        rec = {k: v for k, v in make_smpl_record(seed=seed * 100_003 + i).items() if k not in RECORD_ASSETS}
+        if records == "npz":
+            np.savez(os.path.join(root, "smpl", name + ".npz"), **rec)
+        else:
+            import joblib
+            joblib.dump(rec, os.path.join(root, "smpl", name + ".pkl"))
+    return root

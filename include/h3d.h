@@ -949,6 +949,26 @@ int h3d_seg_loss_bwd(const float* x, const int64_t* x_strides, const int64_t* la
                      const float* grad_out, float scale, float* dx, const int64_t* dx_strides, int B, int H, int W, int L, int kind,
                      h3d_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Dataset ingest == the item transform of SHHQDataset.__getitem__ (lib/data/datasets.py:282-309: white background, ToTensor,
+ * Normalize(0.5, 0.5), bilinear Resize; cv2.resize(INTER_NEAREST) and the label shift) on decoded uint8 images, for a batch, in one
+ * launch.  No atomics, fixed evaluation order: bit-identical between runs, and an item's result does not depend on its batch.
+ *   rgb [B,Hs,Ws,3], mask [B,Hs,Ws], seg [B,Hs,Ws] uint8, dense  ->  images [B,3,H,W] fp32, masks [B,1,H,W] fp32,
+ *   body_segments [B,H,W] int64.
+ * Source value of a pixel: v = u * (2/255) - 1 (product, then difference, each rounded to fp32; 255 -> exactly 1), with u = 255
+ * wherever mask == 0 (the white background, applied at SOURCE resolution); the mask takes the same map without that step;
+ * geo_only != 0: the three image channels are the mask.
+ * Bilinear, align_corners = False, no antialiasing, any ratio; integer source coordinates per axis (output o of n_out from n_src):
+ *   num = max((2o+1) n_src - n_out, 0), den = 2 n_out, i0 = num / den, i1 = min(i0 + 1, n_src - 1), lambda = (num - i0 den) / den;
+ *   value = lerp_y(lerp_x(v00, v01), lerp_x(v10, v11)), lerp(a, b) = fma(lambda, b - a, a).
+ * Labels: nearest, source (min(y Hs / H, Hs-1), min(x Ws / W, Ws-1)) in integers; output 1 where seg == 0, else seg + 1 (label 255
+ * gives 256: the reference's uint8 sum would wrap it to 0; no dataset carries it).
+ * Stores are 16-byte vectors when W % 4 == 0 and the outputs are 16-byte aligned; Hs = 2H, Ws = 2W with 8-byte aligned inputs reads
+ * 8-byte words as well.  Every other shape and alignment is valid and takes the byte path, with equal results.
+ * B*Hs*Ws*3, B*3*H*W, 2*H*Hs and 2*W*Ws must fit int32. */
+int h3d_ingest(const uint8_t* rgb, const uint8_t* mask, const uint8_t* seg, float* images, float* masks, int64_t* body_segments,
+               int B, int Hs, int Ws, int H, int W, int geo_only, h3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
