@@ -45,6 +45,20 @@ inline int64_t persistent_wgs(int64_t groups, int B, int per_cu) {
     return n < 1 ? 1 : n;
 }
 
+// Work counters of a persistent launch (synthesis_x3.hip, field_x3.hip): a workgroup of batch item b starts at index blockIdx.x
+// and takes every further index as gridDim.x + atomic_add(counter[b], 1) -- a workgroup on a faster XCD comes back sooner and
+// takes more.  Returns int[B] of device memory, zeroed on `st` in front of the launch that follows; nullptr (error set) on failure.
+// The blocks come out of one pool per device, allocated at the first call and handed out round robin (a host-side atomic cursor:
+// no allocation and no synchronisation per call, any number of host threads and streams).  A block is handed out again when the
+// cursor has gone once round the pool: with kWorkCounterPool ints and batches of at most kWorkCounterMaxB that is after at least
+// kWorkCounterPool / kWorkCounterMaxB - 1 = 15 later launches of the largest batch the engines accept, after 65 535 later launches
+// at the 16 items of the flagship workload -- the depth of launches in flight behind one another, over all streams of a device,
+// that the pool covers.
+constexpr int kWorkCounterPool = 1 << 20;
+constexpr int kWorkCounterMaxB = 65535;
+static_assert(kWorkCounterPool / kWorkCounterMaxB - 1 >= 15, "work-counter pool: fewer than 15 launches between two uses of a block");
+int* work_counters(int B, hipStream_t st);
+
 // Function attributes are per device: raise the dynamic-LDS limit of `kernel` to the full 160 KB once per
 // (expansion site = kernel instantiation, device).  Idempotent, so a race between two host threads is harmless.
 #define H3D_ALLOW_MAX_LDS(kernel)                                                                         \

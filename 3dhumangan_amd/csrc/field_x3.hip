@@ -122,7 +122,7 @@ struct Args {
     int64_t N;
     int Hd, F, geo_stride, S, clamp_mode, last_back, white_back;
     int R, log2S;        // fused: rays per batch item; log2(S) when S <= 32 (a power of two), else -1
-    int n_groups;        // unit groups (4 wave units each) per sample; a workgroup walks blockIdx.x, + gridDim.x, ..
+    int n_groups;        // unit groups (4 wave units each) per sample
     float input_scaler;
     LayoutX3 L;
     // GEOIN (A4 inside the kernel): the nearest-vertex index of every sample and the pose tables the features are built from
@@ -141,6 +141,7 @@ struct Args {
     int* ref_count;              // [B]
     int ref_cap, ref_mode;
     float ref_eps, ref_scale;
+    int* work;                   // int[B], zero at launch: the unit groups of item b are handed out on demand (h3d::work_counters, common.hpp)
 };
 
 constexpr int kHeadPad = 64;       // bytes behind every head's fragment rows in LDS (bank staggering)
@@ -504,11 +505,22 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
                       "+v"(a_weights), "+v"(a_out));
     if constexpr (GEOIN) asm volatile("" : "+v"(a_nn), "+v"(a_vik), "+v"(a_tpose), "+v"(a_verts));
 
-    // Persistent workgroups: the sample's tables above are built once, then the workgroup walks the unit groups blockIdx.x,
-    // blockIdx.x + gridDim.x, .. with the weight ring running across them (the stream wraps at the end of every step).
+    // Persistent workgroups: the sample's tables above are built once, then the workgroup walks unit groups with the weight ring
+    // running across them (the stream wraps at the end of every step).  It starts at unit group blockIdx.x and takes every further
+    // one from the item's work counter (gridDim.x + the counter's old value), so that workgroups on a faster XCD take more of them
+    // and the launch does not end with the slowest XCD.  Thread 0 asks for the next index at the top of a unit group (an
+    // address-space-1 atomic, as ref_count), parks it in LDS at the end (the last word of the padding behind the fourth head's
+    // rows), and the four waves read it behind a barrier: all of them walk the same unit groups, which the ring's barriers and the
+    // ray head's flush (nray) need.
+    gi32 work = (gi32)A.work + b;
+    int n_wgs = (int)gridDim.x;
+    asm volatile("" : "+v"(work), "+v"(n_wgs));
+    int* const next_slot = reinterpret_cast<int*>(ring_lds) - 1;
     int nray = 0;                 // RAYHEAD: rays this wave has parked since its last flush (the same in all four waves)
 #pragma unroll 1
-    for (int ug = blockIdx.x; ug < n_groups; ug += gridDim.x) {
+    for (int ug = blockIdx.x; ug < n_groups;) {
+    int fetched = 0;
+    if (t == 0) fetched = __hip_atomic_fetch_add(work, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     int64_t uidx = (int64_t)ug * 4 + wave;                  // this wave's unit
     if constexpr (FUSED) {
         if (ref_mode == 2) {                                // refinement launch: the unit listed in slot ug * 4 + wave (or none)
@@ -897,11 +909,15 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
         }
         }   // per-sample head
     }
+    // ---- unit-group boundary: the index asked for at the top of this unit group, the same in all four waves
+    if (t == 0) *next_slot = n_wgs + fetched;
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // (the shape every barrier of a ring kernel has: tests/test_abi.py)
+    const int ug_next = __builtin_amdgcn_readfirstlane(*next_slot);
     if constexpr (RAYHEAD) {
         // ---- deferred feature head: after 32 rays, and on the workgroup's last trip, the wave runs Wf once over its parked rows.
         //      The four waves get here on the same trips (uniform control flow around the ring); the flush itself uses no barrier.
         ++nray;
-        if (nray == 32 || n_groups - ug <= (int)gridDim.x) {
+        if (nray == 32 || ug_next >= n_groups) {
             // the wave's own hbar stores have reached the L2, and the reloads below do not hit stale lines of the vector cache
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -1005,6 +1021,7 @@ __global__ __launch_bounds__(256, 1) void field_x3_kernel(Args A) {
             nray = 0;
         }
     }
+    ug = ug_next;
     }   // unit groups
     ring.drain();
 }
@@ -1026,6 +1043,8 @@ int launch_one(Args A, int B, int64_t groups, hipStream_t st) {
     int64_t per_sample = h3d::persistent_wgs(groups, B, 4);
     // refinement launch: a handful of listed units per batch item (workgroups beyond the list leave at once)
     if (A.ref_mode == 2) per_sample = std::max<int64_t>(1, std::min<int64_t>((A.ref_cap + 3) / 4, 8));
+    A.work = h3d::work_counters(B, st);
+    if (!A.work) return H3D_ELAUNCH;
     h3d::pre_launch();
     hipLaunchKernelGGL((field_x3_kernel<NT, FUSED, X2, GEOIN, RAYHEAD>), dim3((unsigned)per_sample, (unsigned)B), dim3(256),
                        lds_bytes(A.L, GEOIN, RAYHEAD), st, A);

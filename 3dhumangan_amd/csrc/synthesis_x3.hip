@@ -47,12 +47,13 @@ struct Args {
     int table_floats, total_stages, g_channels, Hr, Wr, n_cst, n_ab, H, W, HdP, C, first_skip, n_pixel_blocks;
     // alignas: with n_tiles packed directly behind n_pixel_blocks the compiler allocates and schedules the whole kernel differently
     // (other VGPR counts; in the shipped x2 variant a ring-stage barrier lost the LDS wait in front of it: tests/test_abi.py)
-    alignas(8) int n_tiles;   // 128-pixel tiles per sample (a workgroup walks tiles blockIdx.x, + gridDim.x, ..)
+    alignas(8) int n_tiles;   // 128-pixel tiles per sample
     int n_walk, tile_first, tile_step;   // the tiles a launch covers: tile_first + i * tile_step, i < n_walk (all of them: 0, 1, n_tiles)
     int heads;             // x2 plans with ToRGB head tables: no zero table of "no ToRGB" weights in LDS (the producers carry no ToRGB)
     int mid_x3;            // x2 plans: the constant-style blocks in front of the first skip block travel / run in the x3 format (MIDX3)
     int* ovf;              // x2: int[B], ovf[b] set to 1 when an activation of sample b leaves the range the f16 planes carry (nullable)
     const int* run_if;     // int[B] (nullable): sample b is skipped when run_if[b] == 0 -- the guarded fallback of the x2 engine
+    int* work;             // int[B], zero at launch: the tiles of sample b are handed out on demand (h3d::work_counters, common.hpp)
 };
 
 // x2 range guard: the hi plane is f16 and the lo plane travels as f16(lo * 2^12) with |lo| <= ulp(hi) / 2, so both planes are
@@ -335,16 +336,30 @@ __global__ __launch_bounds__(256, 1) void synthesis_x3_kernel(Args A) {
     const int n_blocks = dget(H3D_MAX_BLOCKS, 0);
     // kernel arguments used late in the kernel, pinned in scalar registers now (the compiler would otherwise re-load them from the
     // kernarg segment where they are used -- see above)
-    int first_skip = A.first_skip, n_pixel_blocks = A.n_pixel_blocks, n_tiles = A.n_tiles;
-    // the tiles of this workgroup: tile_first + (blockIdx.x + i * gridDim.x) * tile_step < n_tiles, as ONE running index
-    int tile_stride = (int)gridDim.x * A.tile_step;
+    int first_skip = A.first_skip, n_pixel_blocks = A.n_pixel_blocks, n_walk = A.n_walk;
+    int tile_first = A.tile_first, tile_step = A.tile_step, n_wgs = (int)gridDim.x;
     float* rgb_out = A.rgb;
-    asm volatile("" : "+s"(first_skip), "+s"(n_pixel_blocks), "+s"(rgb_out), "+s"(n_tiles), "+s"(tile_stride));
-    // Persistent workgroups: a workgroup walks the 128-pixel tiles blockIdx.x, blockIdx.x + gridDim.x, .. of its sample with the
-    // tables above staged once and the weight ring running across tile boundaries (the stream wraps exactly at the end of the
-    // network, so the first stages of the next tile are prefetched under the last layers of this one).
+    int* work_ = A.work + b;
+    // n_wgs and work_ (and Gb_ below) are pinned in VECTOR registers: with a second address built from b pinned in scalar
+    // registers the compiler computes b on the VALU and then rejects the scalar pins ("illegal VGPR to SGPR copy"), and the
+    // variants that compile with scalar pins spill 1-5 SGPRs where this one spills none (profiles/r8_kernel_resource_usage.txt)
+    asm volatile("" : "+s"(first_skip), "+s"(n_pixel_blocks), "+s"(rgb_out), "+s"(n_walk), "+s"(tile_first), "+s"(tile_step),
+                      "+v"(n_wgs), "+v"(work_));
+    // Persistent workgroups: a workgroup walks 128-pixel tiles of its sample with the tables above staged once and the weight ring
+    // running across tile boundaries (the stream wraps exactly at the end of the network, so the first stages of the next tile are
+    // prefetched under the last layers of this one).
+    // The tiles of a launch are tile_first + i * tile_step, i < n_walk.  A workgroup starts at i = blockIdx.x and takes every
+    // further i from the sample's work counter (n_wgs + the counter's old value): the XCDs of a socket at its power limit do not
+    // run at one clock, and with a fixed share per workgroup the launch ended with the slowest of them.  Thread 0 asks for the
+    // next index at the top of a tile (an address-space-1 atomic: a FLAT one would degrade every LDS wait, see the RGB stores
+    // below), parks it in a spare descriptor slot in LDS at the end, and the four waves read it behind a barrier: all of them
+    // walk the same tiles, which the ring's barriers need.
+    int* const next_slot = dtab + H3D_MAX_BLOCKS * kDescInts + 3;       // row H3D_MAX_BLOCKS uses fields 0 .. 2 only
 #pragma unroll 1
-    for (int tile = A.tile_first + (int)blockIdx.x * A.tile_step; tile < n_tiles; tile += tile_stride) {
+    for (int walk = (int)blockIdx.x; (unsigned)walk < (unsigned)n_walk;) {
+    const int tile = tile_first + walk * tile_step;
+    int fetched = 0;
+    if (t == 0) fetched = __hip_atomic_fetch_add((__attribute__((address_space(1))) int*)work_, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int64_t p_tile = ((int64_t)tile * 4 + wave) * 32;
     int64_t p = p_tile + m;
     const bool okp = p < HW;
@@ -356,7 +371,7 @@ __global__ __launch_bounds__(256, 1) void synthesis_x3_kernel(Args A) {
     const int y0 = min((int)sy, A.Hr - 1), x0 = min((int)sx, A.Wr - 1);
     const float ty = sy - (float)y0, tx = sx - (float)x0;
     const float* Gb_ = A.G + (int64_t)b * A.Hr * A.Wr * A.g_channels;
-    asm volatile("" : "+s"(Gb_));                  // loaded from the kernarg segment here, not where it is first used
+    asm volatile("" : "+v"(Gb_));                  // loaded from the kernarg segment here, not where it is first used
     const float* __restrict__ Gb = Gb_;
     // Bilinear resize of the low-res maps as a matrix product (the usual case: the wave's 32 pixels lie in one image
     // row and touch at most 8 low-res columns): D[ch][px] = sum_k T[k][ch] * wi[k][px] over the 16 texels
@@ -647,6 +662,13 @@ __global__ __launch_bounds__(256, 1) void synthesis_x3_kernel(Args A) {
         // s_waitcnt lgkmcnt(0) -- the weight-fragment look-ahead was drained at every table read (round 5, found in the ISA)
         if (okp && h == 0) ((__attribute__((address_space(1))) float*)rgb_out)[((int64_t)b * 3 + c) * HW + p] = v;
     }
+    // ---- tile boundary: the index asked for at the top of this tile, the same in all four waves
+    //      (the compiler puts s_waitcnt vmcnt(0) in front of this use, in wave 0 only: once per tile it waits for the RGB stores
+    //      above and the ring's stages in flight.  Parking the index earlier in the tile made it hoist the wait to the top of
+    //      the tile, behind the atomic itself.)
+    if (t == 0) *next_slot = n_wgs + fetched;
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // (the shape every barrier of a ring kernel has: tests/test_abi.py)
+    walk = __builtin_amdgcn_readfirstlane(*next_slot);
     }   // tiles
     if constexpr (X2) {
         // sticky range flag of this sample: an activation beyond the f16 planes' range anywhere in its tiles (NaN compares false below too)
@@ -672,6 +694,8 @@ int launch_variant(Args A, int B, int64_t groups, hipStream_t st) {
     // once per ~n_tiles * B / (4 CUs) tiles while the tail of the launch stays short
     // (a fallback launch -- run_if -- usually redoes ONE sample of the batch: that sample's workgroups must fill the chip by themselves)
     const int64_t per_sample = A.run_if ? std::min<int64_t>(groups, h3d::compute_units()) : h3d::persistent_wgs(groups, B, 4);
+    A.work = h3d::work_counters(B, st);
+    if (!A.work) return H3D_ELAUNCH;
     h3d::pre_launch();
     hipLaunchKernelGGL((synthesis_x3_kernel<NT, DEPTH, X2, HEADS, MIDX3>), dim3((unsigned)per_sample, (unsigned)B), dim3(256),
                        lds_bytes(A, NT, DEPTH + (X2 ? 1 : 0)), st, A);
