@@ -4,37 +4,9 @@ and the evidence that the scheme sits well inside the 1e-3 budget before any ker
 import pytest
 import torch
 
+from _field_arithmetic import _field
 from conftest import load_golden, rel_err
 from x2_emulation import q_e2m3, x2_matmul, x3_matmul
-
-
-def _field(state, points, freq, phase, geo, dirs, input_scaler, mm):
-    """lib/implicit_funcitions/modulated.py:41-75 with the hidden-layer contractions routed through `mm` (float64 elsewhere)."""
-    p = "neural_field."
-    st = {k: v.double() for k, v in state.items()}
-    hd = st[p + "sigma_layer.weight"].shape[1]
-
-    def lin(name, x, hidden=False, cols=None):
-        W, b = st[p + name + ".weight"], st[p + name + ".bias"]
-        if cols is not None:
-            W = W[:, cols]
-        return (mm(x, W) if hidden else x @ W.t()) + b
-
-    f = (freq.double() * 15 + 30).unsqueeze(1)
-    ph = phase.double().unsqueeze(1)
-    a = torch.sin(30.0 * lin("first_layer_coord.layer", points.double() * input_scaler))
-    g = torch.sin(30.0 * lin("first_layer_mod.layer", geo.double()))
-    x = torch.cat([a, g], dim=-1)
-    for k in range(4):
-        sl = slice(k * hd, (k + 1) * hd)
-        x = torch.sin(f[..., sl] * lin(f"network.{k}.layer", x, hidden=True) + ph[..., sl])
-    sigma = lin("sigma_layer", x)
-    Wc, bc = st[p + "color_layer_sine.layer.weight"], st[p + "color_layer_sine.layer.bias"]
-    c = mm(x, Wc[:, 3:]) + dirs.double() @ Wc[:, :3].t() + bc
-    c = torch.sin(f[..., -hd:] * c + ph[..., -hd:])
-    rgb = torch.sigmoid(lin("color_layer_linear", c))
-    feat = lin("feature_layer_linear", c, hidden=True)
-    return torch.cat([rgb, feat, sigma], dim=-1)
 
 
 def test_e2m3_quantiser():
