@@ -166,6 +166,8 @@ _SIGNATURES = {
     "h3d_seg_loss_fwd": (C.c_int, [_p, C.POINTER(_l), _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "h3d_seg_loss_bwd": (C.c_int, [_p, C.POINTER(_l), _p, _p, _p, _p, _f, _p, C.POINTER(_l), _i, _i, _i, _i, _i, _p]),
     "h3d_ingest": (C.c_int, [_p] * 6 + [_i] * 6 + [_p]),
+    "h3d_isosurface_count": (C.c_int, [_p, _i, _i, _i, _f, _p, _p, _p]),
+    "h3d_isosurface_emit": (C.c_int, [_p, _i, _i, _i, _f, C.POINTER(_f), C.POINTER(_f), _p, _p, _p, _l, _p, _l, _p]),
 }
 
 

@@ -14,7 +14,9 @@ optionally orig_cam [n,4]) with `--smpl-model PATH.npz` (the arrays of lib/compo
 faces_to_labels, optionally joints_index) poses the body instead of turning the camera: all poses go through the SMPL
 forward and smpl_conditions on the device in one batch, and there is one frame per pose -- the camera fixed, or, with
 `--n_angles K` given as well, frame i at angle i mod K of the sweep.  `--pose-sequence synthetic` takes the procedural
-model and motion of `synthetic.py` (`--n_poses` frames) and needs no file.
+model and motion of `synthetic.py` (`--n_poses` frames) and needs no file.  `--save mesh` writes the body's surface instead of
+images: the iso-surface of the field's density (Map3DGenerator.extract_mesh) for the seed's latent and conditions, before any
+camera rotation, as `{seed:03d}_mesh.ply` -- one file per pose, `{seed:03d}_mesh_{i:03d}.ply`, with `--pose-sequence`.
 
     python -m 3dhumangan_amd.apps.sample_from_generator --config MAP3DBN --seeds 1 2 --n_angles 8 --save png
 """
@@ -28,6 +30,7 @@ import torch
 from .. import checkpoints, configs, synthetic
 from ..lib import data as lib_data
 from ..lib import generators as lib_generators
+from ..lib.components.mesh_io import write_ply
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
@@ -140,6 +143,19 @@ def load_smpl_record(path, dev):
     return cond, pre
 
 
+@torch.no_grad()
+def generate_meshes(generator, config, seed, conditions, resolution, level=None):
+    """The surface of every item of the batched `conditions` for the latent of `seed` -> list of (vertices, faces).  The RNGs are
+    seeded anew per item, as generate_pose_frames does per frame: a mesh belongs to the frame of the same seed and pose."""
+    dev = generator.device
+    meshes = []
+    for i in range(conditions["vertices"].shape[0]):
+        z = latent_for_seed(seed, config["latent_dim"]).to(dev)
+        body = {k: conditions[k][i:i + 1].to(dev) for k in generator.MESH_CONDITIONS}
+        meshes += generator.extract_mesh(z, body, level=level, resolution=resolution, **config)
+    return meshes
+
+
 def _save(path_stem, frames, mode):
     from PIL import Image
     if mode == "png":
@@ -173,7 +189,10 @@ def main(argv=None):
     ap.add_argument("--lock_view_dependence", default=None)
     ap.add_argument("--n_angles", type=int, default=None, help="camera angles of the sweep (default 40)")
     ap.add_argument("--back_and_forth", default=False, action="store_true")
-    ap.add_argument("--save", type=str, default="png", choices=["mp4", "png", "gif"])
+    ap.add_argument("--save", type=str, default="png", choices=["mp4", "png", "gif", "mesh"])
+    ap.add_argument("--mesh_resolution", type=int, default=256, help="--save mesh: grid nodes along the body box's longest axis")
+    ap.add_argument("--mesh_level", type=float, default=None, help="--save mesh: the density of the surface (default: the "
+                    "density at which one integration step of the render is half opaque)")
     ap.add_argument("--stitch", default=False, action="store_true")
     ap.add_argument("--synthetic-conditions", action="store_true", default=True)
     ap.add_argument("--smpl-record", type=str, default=None, help="an .npz SMPL record (+ joints_index, smpl_tpose_vertices, "
@@ -223,6 +242,18 @@ def main(argv=None):
         sequence, preprocessor = load_pose_sequence(opt.smpl_model, opt.pose_sequence, device, opt.n_poses)
         pan, tilt = camera_sweep(opt.n_angles, math.pi / 6, 0, opt.back_and_forth) if sweep_given else (torch.zeros(1), torch.zeros(1))
     for k, seed in enumerate(opt.seeds):
+        if opt.save == "mesh":
+            if opt.pose_sequence is not None:
+                data = sequence
+            elif opt.dataroot is not None:
+                data = {k: v[None] for k, v in dataset[order[k % len(order)]].items()}
+            else:
+                data = record if opt.smpl_record is not None else synthetic.make_conditions(1, 6890, seed=seed)
+            meshes = generate_meshes(generator, config, seed, data, opt.mesh_resolution, opt.mesh_level)
+            for i, (vertices, faces) in enumerate(meshes):
+                name = f"{seed:03d}_mesh_{i:03d}.ply" if opt.pose_sequence is not None else f"{seed:03d}_mesh.ply"
+                write_ply(os.path.join(out_dir, name), vertices, faces)
+            continue
         if opt.pose_sequence is not None:
             frames, semantics = generate_pose_frames(generator, preprocessor, config, seed, sequence, pan, tilt)
         else:

@@ -19,12 +19,14 @@ RNG; ``jitter=`` / ``noise=`` kwargs inject explicit tensors instead (used by th
 import math
 import os
 
+import numpy as np
 import torch
 import torch.nn as nn
 
 from ... import _lib
 from ..._stages import stage
 from ..components import smpl
+from ..components.isosurface import marching_tetrahedra
 from ..components.ops.bias_act import bias_act
 from . import volume_rendering as vr
 from .differentiable import synthesis_forward
@@ -697,12 +699,9 @@ class Map3DGenerator(nn.Module):
         with torch.cuda.device(latent.device):
             return self._staged_forward(latent, conditions, render_height, render_width, truncation_psi, **kwargs)
 
-    def _staged_forward(self, latent, conditions, render_height, render_width, truncation_psi, **kwargs):
-        no_render = kwargs.get("disable_render", False)
-        if no_render:
-            self._norender_checks(kwargs, False)
-        num_steps = kwargs.get("num_steps", 24)
-        B = latent.shape[0]
+    def _truncated_mapping(self, latent, truncation_psi, kwargs):
+        """reference :289-301: the mapping networks, then the truncation trick towards the mean of 10 000 latents (``avg_latent=`` in
+        kwargs, or the cached one with cache_avg_latent=True, else drawn here) -> (latent, frequencies, phases, styles)."""
         fr, ph, styles = self._mapping(latent, kwargs)
         if truncation_psi < 1.0:
             avg = kwargs.get("avg_latent")
@@ -715,6 +714,15 @@ class Map3DGenerator(nn.Module):
             ph = ap + truncation_psi * (ph - ap)
             latent = az + truncation_psi * (latent - az)
             styles = ast + truncation_psi * (styles - ast)
+        return latent, fr, ph, styles
+
+    def _staged_forward(self, latent, conditions, render_height, render_width, truncation_psi, **kwargs):
+        no_render = kwargs.get("disable_render", False)
+        if no_render:
+            self._norender_checks(kwargs, False)
+        num_steps = kwargs.get("num_steps", 24)
+        B = latent.shape[0]
+        latent, fr, ph, styles = self._truncated_mapping(latent, truncation_psi, kwargs)
         rk = {k: v for k, v in kwargs.items() if k not in ("coarse_steps", "fine_steps", "render_width", "render_height",
                                                            "staged", "avg_latent", "cache_avg_latent")}
         feature_hw = (render_height, render_width)
@@ -741,3 +749,66 @@ class Map3DGenerator(nn.Module):
         out.update({"depths": depth_map if kwargs.get("keep_depth_on_device", False) else depth_map.cpu(),
                     "skeletons": conditions["skeletons_xyz"]})
         return out
+
+    # ------------------------------------------------------------------ geometry export
+    MESH_CONDITIONS = ("skeletons_xyz", "vertices", "tpose_vertices", "fk_matrices", "lbs_weights")
+
+    @torch.no_grad()
+    def density_grid(self, latent, conditions, resolution=256, margin=0.1, truncation_psi=1.0, max_points=2 ** 21, precision=None,
+                     **config):
+        """The density of the field on a regular grid around each body -> (sigma fp32 [B,Nx,Ny,Nz], origin [B,3], spacing [B,3]);
+        node (i, j, k) of item b lies at origin[b] + spacing[b] * (i, j, k), in the world frame of conditions["vertices"].
+
+        Mapping and truncation are staged_forward's own (avg_latent= / cache_avg_latent= honoured), so the grid belongs to the image
+        the same latent gives.  Per item the axis-aligned box of the SMPL vertices is grown on every side by `margin` x its longest
+        edge; the voxels are cubic, `resolution` nodes span the longest axis of the grown box and the other axes take as many nodes
+        as cover it at that spacing; all items share (Nx, Ny, Nz), the largest count over the batch per axis.  The field runs on
+        chunks of at most `max_points` points (over the batch) through get_geo_features and the engine `precision` (None: the
+        field's own) and only its density channel is kept: the [N, F+4] tensor never exists for the grid.  The density head does
+        not read the view direction.  Of `conditions` only MESH_CONDITIONS are read -- no camera."""
+        if not latent.is_cuda:
+            _lib.need_cuda(latent)
+        if int(resolution) < 2:
+            raise ValueError(f"density_grid: resolution={resolution} (nodes along the longest axis) must be at least 2")
+        with torch.cuda.device(latent.device):
+            _, fr, ph, _ = self._truncated_mapping(latent, truncation_psi, config)
+            mesh = tuple(conditions[k] for k in self.MESH_CONDITIONS)
+            verts = conditions["vertices"].float()
+            B, dev = verts.shape[0], verts.device
+            # the grid's frame, on the host in float64 (the node counts are shapes: one read of 6 B numbers)
+            lo, hi = (t.double().cpu().numpy() for t in (verts.amin(dim=1), verts.amax(dim=1)))
+            grow = margin * (hi - lo).max(axis=1, keepdims=True)
+            lo, extent = lo - grow, (hi - lo) + 2 * grow
+            step = extent.max(axis=1) / (int(resolution) - 1)                                  # [B]
+            counts = np.ceil(extent / step[:, None] - 1e-6).astype(np.int64) + 1               # nodes that cover the box
+            Nx, Ny, Nz = (max(2, int(n)) for n in counts.max(axis=0))
+            origin = torch.as_tensor(lo, dtype=torch.float32).to(dev)
+            spacing = torch.as_tensor(np.repeat(step[:, None], 3, axis=1), dtype=torch.float32).to(dev)
+            N = Nx * Ny * Nz
+            sigma = torch.empty(B, N, dtype=torch.float32, device=dev)
+            chunk = max(1, int(max_points) // B)
+            scaler = 2.0 / self.side_length
+            for start in range(0, N, chunk):
+                n = torch.arange(start, min(start + chunk, N), device=dev)
+                ijk = torch.stack([n // (Ny * Nz), (n // Nz) % Ny, n % Nz], dim=-1).float()    # node id = (ix Ny + iy) Nz + iz
+                pts = (origin[:, None] + spacing[:, None] * ijk[None]).contiguous()
+                geo = self.get_geo_features(pts, *mesh)
+                out = self.neural_field(pts, fr, ph, geo, None, input_scaler=scaler, differentiable=False, precision=precision)
+                sigma[:, start:start + n.shape[0]] = out[..., -1]
+            return sigma.reshape(B, Nx, Ny, Nz), origin, spacing
+
+    @torch.no_grad()
+    def extract_mesh(self, latent, conditions, level=None, **config):
+        """The iso-surface of density_grid(latent, conditions, **config) at `level` as one (vertices fp32 [V,3], faces int32 [T,3])
+        per item, in the world frame of conditions["vertices"], normals pointing out of the body (marching tetrahedra on the
+        device, lib/components/isosurface.py).  level=None: ln 2 * num_steps / (ray_end - ray_start), the density at which one
+        coarse integration step of the render is half opaque (1 - exp(-sigma * delta) = 1/2)."""
+        clamp = config.get("clamp_mode", "relu")
+        if clamp != "relu":
+            raise NotImplementedError(f"extract_mesh: clamp_mode={clamp!r} is not supported: only with 'relu' is the raw output of "
+                                      "the density head the density the renderer integrates (above zero)")
+        if level is None:
+            level = math.log(2.0) * config.get("num_steps", 24) / (config["ray_end"] - config["ray_start"])
+        sigma, origin, spacing = self.density_grid(latent, conditions, **config)
+        with torch.cuda.device(sigma.device):
+            return [marching_tetrahedra(sigma[b], level, o, s) for b, (o, s) in enumerate(zip(origin.tolist(), spacing.tolist()))]

@@ -969,6 +969,36 @@ int h3d_seg_loss_bwd(const float* x, const int64_t* x_strides, const int64_t* la
 int h3d_ingest(const uint8_t* rgb, const uint8_t* mask, const uint8_t* seg, float* images, float* masks, int64_t* body_segments,
                int B, int Hs, int Ws, int H, int W, int geo_only, h3d_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Iso-surface of a density volume as an indexed triangle mesh: marching tetrahedra on the Kuhn (Freudenthal) split of every cell.
+ * Two launches; the caller takes the exclusive prefix sums of the counts between them and reads their totals (V, T) to size the
+ * outputs.  No atomics: every vertex and face has its slot from the prefix sums, so two runs give bit-identical tensors.
+ *   volume [Nx,Ny,Nz] fp32 dense; node id = (ix Ny + iy) Nz + iz; a node is inside iff value > level (value == level and NaN: outside).
+ *   Edges: lower node + one of the directions (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1), type 0..6 in this order;
+ *          edge id = node id * 7 + type; an edge that leaves the grid does not exist.  Every vertex lies on one edge whose ends are on
+ *          different sides: from node p (value a) along d to value b, s = (level - a) / (b - a), position origin + spacing (p + s d),
+ *          fp32.  Vertices come out in ascending edge id.
+ *   Cells: id = (ix (Ny-1) + iy) (Nz-1) + iz, six tetrahedra each: for the k-th permutation pi of the axes (0,1,2) in lexicographic
+ *          order, v0 = (0,0,0), v1 = v0 + e_pi1, v2 = v1 + e_pi2, v3 = (1,1,1) -- translation invariant, so neighbouring cells agree
+ *          on every face diagonal.  One or three corners inside: one triangle, the three cut edges.  Two inside i0 < i1, two outside
+ *          o0 < o1 (in v0..v3 order): the quad as (i0o0, i0o1, i1o1) and (i0o0, i1o1, i1o0).  The normal points from inside to
+ *          outside (towards lower values); a wrong orientation is mended by swapping the last two corners, decided from the case and
+ *          the parity of pi, never from positions (a triangle that collapses because a node value equals the level keeps its sense).
+ *          Faces come out in ascending (cell id, tetrahedron, triangle).
+ *   h3d_isosurface_count  vertex_counts [Nx*Ny*Nz] int32 = crossing edges whose lower node it is (0..7); triangle_counts
+ *                         [(Nx-1)(Ny-1)(Nz-1)] int32 = triangles of the cell (0..12).
+ *   h3d_isosurface_emit   vertex_offsets [Nx*Ny*Nz] int32 and triangle_offsets [cells] int64: the exclusive prefix sums of the counts
+ *                         of the same volume and level; origin[3], spacing[3]: HOST floats; vertices [V,3] fp32, faces [T,3] int32,
+ *                         V, T >= 1 (an empty surface needs no emit).  Every store is guarded by V and T: offsets that do not belong
+ *                         to the volume give a wrong mesh, never a store out of range.  On non-finite values the positions are
+ *                         unspecified; every index stays in range.
+ * Both stage tiles of 8 x 8 x 16 nodes with their upper halo in LDS.  Nx, Ny, Nz >= 2 and 7 Nx Ny Nz < 2^31 (edge ids are int32). */
+int h3d_isosurface_count(const float* volume, int Nx, int Ny, int Nz, float level, int32_t* vertex_counts, int32_t* triangle_counts,
+                         h3d_stream_t stream);
+int h3d_isosurface_emit(const float* volume, int Nx, int Ny, int Nz, float level, const float* origin, const float* spacing,
+                        const int32_t* vertex_offsets, const int64_t* triangle_offsets, float* vertices, int64_t V, int32_t* faces,
+                        int64_t T, h3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
