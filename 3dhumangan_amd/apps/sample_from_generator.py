@@ -17,6 +17,11 @@ forward and smpl_conditions on the device in one batch, and there is one frame p
 model and motion of `synthetic.py` (`--n_poses` frames) and needs no file.  `--save mesh` writes the body's surface instead of
 images: the iso-surface of the field's density (Map3DGenerator.extract_mesh) for the seed's latent and conditions, before any
 camera rotation, as `{seed:03d}_mesh.ply` -- one file per pose, `{seed:03d}_mesh_{i:03d}.ply`, with `--pose-sequence`.
+`--mesh_normals` adds per-vertex normals (nx ny nz: the normalised gradient of the density) to those files, `--mesh_color_views K
+[--mesh_color_range DEG, default 30]` per-vertex colours as well (red green blue; it implies the normals): K frames panned evenly
+over +-DEG, each made as a frame of this app is made (RNGs seeded anew, the latent, the preprocessor, staged_forward -- the view at
+angle 0 is the frame the app saves for the seed and pose), carried onto the vertices by Map3DGenerator.project_views.  A vertex no
+view sees stays at colour 0 (mid grey).  With random-init weights the frames are noise and so are the colours.
 
     python -m 3dhumangan_amd.apps.sample_from_generator --config MAP3DBN --seeds 1 2 --n_angles 8 --save png
 """
@@ -156,6 +161,33 @@ def generate_meshes(generator, config, seed, conditions, resolution, level=None)
     return meshes
 
 
+@torch.no_grad()
+def generate_textured_meshes(generator, preprocessor, config, seed, conditions, resolution, level=None, n_views=0, view_range=30.0):
+    """generate_meshes with normals and, for n_views > 0, colours -> list of dict(vertices, faces, normals, colors, coverage).
+    The colours come from `n_views` frames panned evenly over +-view_range degrees (one view: angle 0), each made as
+    generate_pose_frames makes a frame -- RNGs seeded anew, the latent drawn, the conditions turned by the preprocessor, staged_forward
+    -- so the view at angle 0 is the frame the app saves for this seed and pose."""
+    dev = generator.device
+    pan = torch.linspace(-math.radians(view_range), math.radians(view_range), n_views) if n_views > 1 else torch.zeros(n_views)
+    meshes = []
+    for i in range(conditions["vertices"].shape[0]):
+        z = latent_for_seed(seed, config["latent_dim"]).to(dev)
+        base = {k: v[i:i + 1].to(dev) for k, v in conditions.items()}
+        base["scales"] = base["scales"].reshape(1)
+        body = {k: base[k] for k in generator.MESH_CONDITIONS}
+        mesh, = generator.extract_textured_mesh(z, body, [], level=level, resolution=resolution, **config)
+        views, frames = [], []
+        for a_h in pan.to(dev):
+            z = latent_for_seed(seed, config["latent_dim"]).to(dev)
+            a_h = a_h.reshape(1, 1)
+            views.append(preprocessor.forward_with_rotation(dict(base), a_h, torch.zeros_like(a_h), torch.zeros_like(a_h), **config))
+            frames.append(generator.mesh_view(z, views[-1], **config))
+        if views:
+            mesh["colors"], mesh["coverage"] = generator.project_views(mesh, views, frames, 0, generator.default_depth_tolerance(config))
+        meshes.append(mesh)
+    return meshes
+
+
 def _save(path_stem, frames, mode):
     from PIL import Image
     if mode == "png":
@@ -173,7 +205,7 @@ def _save(path_stem, frames, mode):
         raise NotImplementedError
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default="MAP3DBN")
     ap.add_argument("--tune", type=str, default="")
@@ -193,6 +225,11 @@ def main(argv=None):
     ap.add_argument("--mesh_resolution", type=int, default=256, help="--save mesh: grid nodes along the body box's longest axis")
     ap.add_argument("--mesh_level", type=float, default=None, help="--save mesh: the density of the surface (default: the "
                     "density at which one integration step of the render is half opaque)")
+    ap.add_argument("--mesh_normals", default=False, action="store_true", help="--save mesh: write per-vertex normals (the "
+                    "normalised gradient of the density) as nx ny nz")
+    ap.add_argument("--mesh_color_views", type=int, default=0, help="--save mesh: colour the vertices from this many frames "
+                    "panned evenly over +-mesh_color_range (red green blue; implies --mesh_normals)")
+    ap.add_argument("--mesh_color_range", type=float, default=30.0, help="--mesh_color_views: half-width of the pan in degrees")
     ap.add_argument("--stitch", default=False, action="store_true")
     ap.add_argument("--synthetic-conditions", action="store_true", default=True)
     ap.add_argument("--smpl-record", type=str, default=None, help="an .npz SMPL record (+ joints_index, smpl_tpose_vertices, "
@@ -202,7 +239,11 @@ def main(argv=None):
     ap.add_argument("--pose-sequence", type=str, default=None, help="an .npz pose sequence (poses [n,J,3], betas, orig_cam) or "
                     "`synthetic`: one frame per pose; the camera is fixed unless --n_angles is given as well")
     ap.add_argument("--n_poses", type=int, default=8, help="frames of the procedural motion of `--pose-sequence synthetic`")
-    opt = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    opt = build_parser().parse_args(argv)
     sweep_given = opt.n_angles is not None
     if opt.n_angles is None:
         opt.n_angles = 40
@@ -212,6 +253,10 @@ def main(argv=None):
         raise ValueError("--pose-sequence, --smpl-record and --dataroot are three ways to give the body: pass one")
     if opt.dataroot is not None and opt.smpl_model is None:
         raise ValueError("--dataroot needs --smpl-model PATH.npz: the SMPL model as plain arrays (the licensed file cannot ship)")
+    if (opt.mesh_normals or opt.mesh_color_views) and opt.save != "mesh":
+        raise ValueError("--mesh_normals and --mesh_color_views go with --save mesh")
+    if opt.mesh_color_views < 0:
+        raise ValueError(f"--mesh_color_views {opt.mesh_color_views}: a number of views, 0 for none")
     config = configs.get_config(opt)
     config = {k: v for k, v in config.items() if type(k) is str}
     config["truncation_psi"] = 0.7
@@ -249,10 +294,15 @@ def main(argv=None):
                 data = {k: v[None] for k, v in dataset[order[k % len(order)]].items()}
             else:
                 data = record if opt.smpl_record is not None else synthetic.make_conditions(1, 6890, seed=seed)
-            meshes = generate_meshes(generator, config, seed, data, opt.mesh_resolution, opt.mesh_level)
-            for i, (vertices, faces) in enumerate(meshes):
+            if opt.mesh_normals or opt.mesh_color_views:
+                meshes = generate_textured_meshes(generator, preprocessor, config, seed, data, opt.mesh_resolution, opt.mesh_level,
+                                                  opt.mesh_color_views, opt.mesh_color_range)
+                meshes = [(m["vertices"], m["faces"], m["normals"], m["colors"]) for m in meshes]
+            else:
+                meshes = generate_meshes(generator, config, seed, data, opt.mesh_resolution, opt.mesh_level)
+            for i, mesh in enumerate(meshes):
                 name = f"{seed:03d}_mesh_{i:03d}.ply" if opt.pose_sequence is not None else f"{seed:03d}_mesh.ply"
-                write_ply(os.path.join(out_dir, name), vertices, faces)
+                write_ply(os.path.join(out_dir, name), *mesh)
             continue
         if opt.pose_sequence is not None:
             frames, semantics = generate_pose_frames(generator, preprocessor, config, seed, sequence, pan, tilt)

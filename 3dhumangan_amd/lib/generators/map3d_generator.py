@@ -26,7 +26,8 @@ import torch.nn as nn
 from ... import _lib
 from ..._stages import stage
 from ..components import smpl
-from ..components.isosurface import marching_tetrahedra
+from ..components.isosurface import marching_tetrahedra, vertex_normals
+from ..components.mesh_color import project_colors
 from ..components.ops.bias_act import bias_act
 from . import volume_rendering as vr
 from .differentiable import synthesis_forward
@@ -812,3 +813,67 @@ class Map3DGenerator(nn.Module):
         sigma, origin, spacing = self.density_grid(latent, conditions, **config)
         with torch.cuda.device(sigma.device):
             return [marching_tetrahedra(sigma[b], level, o, s) for b, (o, s) in enumerate(zip(origin.tolist(), spacing.tolist()))]
+
+    @torch.no_grad()
+    def extract_textured_mesh(self, latent, conditions, views, level=None, depth_tolerance=None, normal_power=2, **config):
+        """extract_mesh with per-vertex attributes -> one dict(vertices, faces, normals, colors, coverage) per item.
+
+        vertices and faces are extract_mesh's; normals are vertex_normals of the same density grid (one density_grid call serves
+        both).  The colour does not live in the field -- the synthesis network makes the appearance -- so it is carried over from
+        images: for every entry of `views` (a conditions dict batched like `conditions`, what CameraPreprocessor.forward_with_rotation
+        returns) staged_forward(latent, view, keep_depth_on_device=True, **config) runs, in list order, and nothing else here draws
+        random numbers: the same seed in front of this call gives the frames the app gives.  Each view's depth map is taken back to
+        the distance along the ray (depth_map * depth_length / 2 + focal / scale) and project_colors (lib/components/mesh_color.py)
+        weighs the views at every vertex: colors fp32 [V,3] in the images' [-1, 1], coverage fp32 [V] = how much the vertex was seen
+        (a vertex no view sees has coverage 0 and colour 0).  views=[] gives colors = coverage = None.
+        depth_tolerance=None: 2 * (ray_end - ray_start) / num_steps, two coarse steps of the render -- the resolution to which its
+        expected depth and the iso-surface can agree."""
+        clamp = config.get("clamp_mode", "relu")
+        if clamp != "relu":
+            raise NotImplementedError(f"extract_textured_mesh: clamp_mode={clamp!r} is not supported: only with 'relu' is the raw output "
+                                      "of the density head the density the renderer integrates (above zero)")
+        if int(normal_power) != normal_power or not 1 <= int(normal_power) <= 8:
+            raise ValueError(f"extract_textured_mesh: normal_power={normal_power} must be an integer 1..8")
+        views = list(views)
+        if level is None:
+            level = math.log(2.0) * config.get("num_steps", 24) / (config["ray_end"] - config["ray_start"])
+        if depth_tolerance is None:
+            depth_tolerance = self.default_depth_tolerance(config)
+        if not 0.0 < float(depth_tolerance) < float("inf"):
+            raise ValueError(f"extract_textured_mesh: depth_tolerance={depth_tolerance} must be positive")
+        sigma, origin, spacing = self.density_grid(latent, conditions, **config)
+        with torch.cuda.device(sigma.device):
+            meshes = []
+            for b, (o, s) in enumerate(zip(origin.tolist(), spacing.tolist())):
+                vertices, faces = marching_tetrahedra(sigma[b], level, o, s)
+                meshes.append(dict(vertices=vertices, faces=faces, normals=vertex_normals(sigma[b], vertices, o, s), colors=None,
+                                   coverage=None))
+            if not views:
+                return meshes
+            frames = [self.mesh_view(latent, view, **config) for view in views]
+            for b, mesh in enumerate(meshes):
+                mesh["colors"], mesh["coverage"] = self.project_views(mesh, views, frames, b, depth_tolerance, normal_power)
+            return meshes
+
+    @staticmethod
+    def default_depth_tolerance(config):
+        """two coarse integration steps of the render, in world units"""
+        return 2.0 * (config["ray_end"] - config["ray_start"]) / config.get("num_steps", 24)
+
+    @torch.no_grad()
+    def mesh_view(self, latent, view, **config):
+        """One view for extract_textured_mesh: staged_forward(latent, view, keep_depth_on_device=True, **config) ->
+        (rgbs fp32 [B,3,H,W] clamped to [-1, 1] as the apps clamp a frame, the distance along each ray fp32 [B,h,w] in world units:
+        staged_forward's normalised depth map taken back, depth_map * depth_length / 2 + focal / scale; it saturates where the map
+        was clamped)."""
+        out = self.staged_forward(latent, view, **dict(config, keep_depth_on_device=True))
+        zc = view["intrinsics"][:, 0, 0] / view["scales"].float()
+        return out["rgbs"].float().clamp(-1, 1), out["depths"][:, 0].float() * (config["depth_length"] / 2.0) + zc.view(-1, 1, 1)
+
+    @staticmethod
+    def project_views(mesh, views, frames, b, depth_tolerance, normal_power=2):
+        """project_colors of item `b` of every view (conditions dicts) and its mesh_view frame onto `mesh` -> (colors, coverage)"""
+        return project_colors(mesh["vertices"], mesh["normals"], torch.stack([im[b] for im, _ in frames]),
+                              torch.stack([d[b] for _, d in frames]), torch.stack([v["intrinsics"][b, 0, 0] for v in views]).float(),
+                              torch.stack([v["scales"][b] for v in views]).float(),
+                              torch.stack([v["cam2world_matrices"][b] for v in views]).float(), depth_tolerance, normal_power)

@@ -999,6 +999,44 @@ int h3d_isosurface_emit(const float* volume, int Nx, int Ny, int Nz, float level
                         const int32_t* vertex_offsets, const int64_t* triangle_offsets, float* vertices, int64_t V, int32_t* faces,
                         int64_t T, h3d_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Per-vertex attributes of a mesh (csrc/mesh_attributes.hip).  Both kernels: one thread per vertex, no atomics, every sum in a fixed
+ * order -- two runs give bit-identical tensors.  Every function below is continuous in the vertex position: no thresholds.
+ *
+ * h3d_isosurface_normals: the normal of the density volume at each vertex.
+ *   volume [Nx,Ny,Nz] fp32 dense as above, origin[3] / spacing[3] HOST floats (spacing > 0), vertices [V,3] fp32.
+ *   Node gradient G(p)_a = (v[p + e_a] - v[p - e_a]) / (2 spacing_a); at the two border planes of axis a the one-sided difference
+ *   over one spacing.  At a vertex x: g = (x - origin) / spacing clamped per axis to [0, N_a - 1], cell c = min(floor(g), N_a - 2),
+ *   fraction f = g - c, and G^(x) = the trilinear interpolation of G over the cell's eight nodes -- continuous across cell faces, so
+ *   a vertex on a grid edge gets the same value whichever neighbouring cell the rounding picks.  A vertex outside the grid takes
+ *   the value of the nearest point of the grid's box; a vertex with a non-finite coordinate has G^ = 0.
+ *   normals [V,3] = -G^ / |G^| (inside is above the level: towards lower values, as the faces of h3d_isosurface_emit are oriented),
+ *   (0,0,0) where |G^| is zero or not finite.  gradient [V,3] = G^ itself, or NULL.
+ *   The eight stencils overlap in 32 distinct values of the 4 x 4 x 4 block around the cell; each is loaded once.  Nx, Ny, Nz >= 2.
+ *
+ * h3d_mesh_project_colors: colours of K rendered views carried onto the vertices, weighted by visibility.
+ *   vertices, normals [V,3] fp32; images [K,3,H,W] fp32 (generator outputs); depths [K,h,w] fp32: the distance along the ray, in
+ *   world units, on the render grid of h3d_ray_setup (rays leave the camera origin through (x, y, focal), x in linspace(-w/h, w/h, w),
+ *   y in linspace(-1, 1, h)); table [K,16] fp32: rows 0..2 of world2cam (12 entries, row major), the camera origin (3), the focal.
+ *   Per view k and vertex x:
+ *     p = world2cam_k x;  ok = p.z > 1e-6;  xn = focal p.x / p.z, yn = focal p.y / p.z;
+ *     u = (xn + w/h) / (2 w/h) (w - 1), v = (yn + 1) / 2 (h - 1)                         (render-grid coordinates)
+ *     t = |x - o_k|, d = (x - o_k) / t;  face = max(0, -n.d) ^ normal_power              (an integer 1..8, repeated multiplication)
+ *     edge = clamp(min(u, w-1-u, v, h-1-v), 0, 1)                                        (fades over the outermost render pixel)
+ *     D = bilinear sample of depths[k] at (u, v), coordinates clamped to the grid
+ *     vis = clamp(1 - |t - D| / depth_tolerance, 0, 1)                                   (a tent, not a step)
+ *     w_k = edge vis face where ok, else 0; a non-finite w_k counts as 0
+ *     c_k = bilinear sample of images[k] at u_i = (u + 1/2) W / w - 1/2, v_i likewise, clamped to the image (the convention of
+ *           h3d_bilinear_resize, align_corners = False); taken where w_k > 0 only
+ *   coverage [V] = sum_k w_k;  colors [V,3] = (sum_k w_k c_k + eps fill) / (coverage + eps), the views summed in ascending k.
+ *   A vertex nobody sees tends to `fill`; coverage says how much it was seen.
+ *   K >= 1, h, w, H, W >= 2, depth_tolerance > 0, eps > 0.  V = 0 is valid for both and launches nothing. */
+int h3d_isosurface_normals(const float* volume, int Nx, int Ny, int Nz, const float* origin, const float* spacing,
+                           const float* vertices, int64_t V, float* normals, float* gradient, h3d_stream_t stream);
+int h3d_mesh_project_colors(const float* vertices, const float* normals, int64_t V, const float* images, int K, int H, int W,
+                            const float* depths, int h, int w, const float* table, float depth_tolerance, int normal_power,
+                            float fill, float eps, float* colors, float* coverage, h3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
