@@ -21,7 +21,11 @@ camera rotation, as `{seed:03d}_mesh.ply` -- one file per pose, `{seed:03d}_mesh
 [--mesh_color_range DEG, default 30]` per-vertex colours as well (red green blue; it implies the normals): K frames panned evenly
 over +-DEG, each made as a frame of this app is made (RNGs seeded anew, the latent, the preprocessor, staged_forward -- the view at
 angle 0 is the frame the app saves for the seed and pose), carried onto the vertices by Map3DGenerator.project_views.  A vertex no
-view sees stays at colour 0 (mid grey).  With random-init weights the frames are noise and so are the colours.
+view sees stays at colour 0 (mid grey).  With random-init weights the frames are noise and so are the colours.  `--save avatar`
+(with `--pose-sequence`) writes ONE rigged mesh per seed, `{seed:03d}_avatar.glb` (binary glTF 2.0): the surface is extracted at pose
+`--avatar_bind_pose` of the sequence, takes the SMPL body's skin weights from its `--avatar_k` nearest body vertices and goes to the
+rest pose (Map3DGenerator.extract_avatar); the file holds the rest mesh with normals (colours with `--mesh_color_views`), the skin, the
+skeleton and every pose of the sequence as a key of one animation -- a viewer plays the motion without the network.
 
     python -m 3dhumangan_amd.apps.sample_from_generator --config MAP3DBN --seeds 1 2 --n_angles 8 --save png
 """
@@ -35,7 +39,7 @@ import torch
 from .. import checkpoints, configs, synthetic
 from ..lib import data as lib_data
 from ..lib import generators as lib_generators
-from ..lib.components.mesh_io import write_ply
+from ..lib.components.mesh_io import write_glb, write_ply
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
@@ -112,9 +116,10 @@ def generate_pose_frames(generator, preprocessor, config, seed, conditions, pan,
     return to_uint8_nhwc(torch.cat(frames).float()), to_uint8_nhwc(torch.cat(semantics).float())
 
 
-def load_pose_sequence(model_path, sequence_path, dev, n_synthetic=8):
+def load_pose_sequence(model_path, sequence_path, dev, n_synthetic=8, return_skeleton=False):
     """--smpl-model / --pose-sequence: -> (conditions of every pose of the sequence, batched on `dev`, a CameraPreprocessor on
-    `dev` with the model's faces and labels).  One SMPL forward and one smpl_conditions call for the whole sequence."""
+    `dev` with the model's faces and labels).  One SMPL forward and one smpl_conditions call for the whole sequence.
+    return_skeleton: a third entry, dict(rest_joints [n,J,3]: the joints of each frame's shaped body at rest, parents [J])."""
     from ..lib.components import smpl as smpl_ops
     if sequence_path == "synthetic" and model_path is None:
         model = synthetic.make_smpl_model()
@@ -134,6 +139,8 @@ def load_pose_sequence(model_path, sequence_path, dev, n_synthetic=8):
     cond = lib_data.smpl_conditions(out, cam.expand(n, 4) if cam.shape[0] == 1 else cam, joints_index, model["v_template"])
     pre = lib_data.CameraPreprocessor(dev)
     pre.init_smpl(torch.as_tensor(model["faces"]), torch.as_tensor(model["faces_to_labels"]))
+    if return_skeleton:
+        return cond, pre, {"rest_joints": out["joints_shaped"], "parents": np.asarray(model["parents"]).reshape(-1).astype(np.int64)}
     return cond, pre
 
 
@@ -162,8 +169,10 @@ def generate_meshes(generator, config, seed, conditions, resolution, level=None)
 
 
 @torch.no_grad()
-def generate_textured_meshes(generator, preprocessor, config, seed, conditions, resolution, level=None, n_views=0, view_range=30.0):
+def generate_textured_meshes(generator, preprocessor, config, seed, conditions, resolution, level=None, n_views=0, view_range=30.0,
+                             avatar_k=None):
     """generate_meshes with normals and, for n_views > 0, colours -> list of dict(vertices, faces, normals, colors, coverage).
+    avatar_k: the meshes come from Map3DGenerator.extract_avatar(k=avatar_k) and carry its rig entries as well.
     The colours come from `n_views` frames panned evenly over +-view_range degrees (one view: angle 0), each made as
     generate_pose_frames makes a frame -- RNGs seeded anew, the latent drawn, the conditions turned by the preprocessor, staged_forward
     -- so the view at angle 0 is the frame the app saves for this seed and pose."""
@@ -175,7 +184,10 @@ def generate_textured_meshes(generator, preprocessor, config, seed, conditions, 
         base = {k: v[i:i + 1].to(dev) for k, v in conditions.items()}
         base["scales"] = base["scales"].reshape(1)
         body = {k: base[k] for k in generator.MESH_CONDITIONS}
-        mesh, = generator.extract_textured_mesh(z, body, [], level=level, resolution=resolution, **config)
+        if avatar_k is None:
+            mesh, = generator.extract_textured_mesh(z, body, [], level=level, resolution=resolution, **config)
+        else:
+            mesh, = generator.extract_avatar(z, body, k=avatar_k, level=level, resolution=resolution, **config)
         views, frames = [], []
         for a_h in pan.to(dev):
             z = latent_for_seed(seed, config["latent_dim"]).to(dev)
@@ -221,7 +233,7 @@ def build_parser():
     ap.add_argument("--lock_view_dependence", default=None)
     ap.add_argument("--n_angles", type=int, default=None, help="camera angles of the sweep (default 40)")
     ap.add_argument("--back_and_forth", default=False, action="store_true")
-    ap.add_argument("--save", type=str, default="png", choices=["mp4", "png", "gif", "mesh"])
+    ap.add_argument("--save", type=str, default="png", choices=["mp4", "png", "gif", "mesh", "avatar"])
     ap.add_argument("--mesh_resolution", type=int, default=256, help="--save mesh: grid nodes along the body box's longest axis")
     ap.add_argument("--mesh_level", type=float, default=None, help="--save mesh: the density of the surface (default: the "
                     "density at which one integration step of the render is half opaque)")
@@ -230,6 +242,9 @@ def build_parser():
     ap.add_argument("--mesh_color_views", type=int, default=0, help="--save mesh: colour the vertices from this many frames "
                     "panned evenly over +-mesh_color_range (red green blue; implies --mesh_normals)")
     ap.add_argument("--mesh_color_range", type=float, default=30.0, help="--mesh_color_views: half-width of the pan in degrees")
+    ap.add_argument("--avatar_k", type=int, default=4, help="--save avatar: body vertices (1..8) whose skin weights a mesh vertex blends")
+    ap.add_argument("--avatar_bind_pose", type=int, default=0, help="--save avatar: the pose of the sequence at which the mesh is "
+                    "extracted and bound; every pose becomes a key of the file's animation")
     ap.add_argument("--stitch", default=False, action="store_true")
     ap.add_argument("--synthetic-conditions", action="store_true", default=True)
     ap.add_argument("--smpl-record", type=str, default=None, help="an .npz SMPL record (+ joints_index, smpl_tpose_vertices, "
@@ -253,8 +268,13 @@ def main(argv=None):
         raise ValueError("--pose-sequence, --smpl-record and --dataroot are three ways to give the body: pass one")
     if opt.dataroot is not None and opt.smpl_model is None:
         raise ValueError("--dataroot needs --smpl-model PATH.npz: the SMPL model as plain arrays (the licensed file cannot ship)")
-    if (opt.mesh_normals or opt.mesh_color_views) and opt.save != "mesh":
+    if (opt.mesh_normals or opt.mesh_color_views) and opt.save != "mesh" and not (opt.save == "avatar" and not opt.mesh_normals):
         raise ValueError("--mesh_normals and --mesh_color_views go with --save mesh")
+    if opt.save == "avatar" and opt.pose_sequence is None:
+        raise ValueError("--save avatar needs the skeleton of the body: pass `--pose-sequence synthetic`, or --pose-sequence PATH.npz "
+                         "with --smpl-model PATH.npz")
+    if opt.save == "avatar" and not 1 <= opt.avatar_k <= 8:
+        raise ValueError(f"--avatar_k {opt.avatar_k}: 1..8 nearest body vertices")
     if opt.mesh_color_views < 0:
         raise ValueError(f"--mesh_color_views {opt.mesh_color_views}: a number of views, 0 for none")
     config = configs.get_config(opt)
@@ -284,9 +304,20 @@ def main(argv=None):
         preprocessor = lib_data.get_preprocessor(device, opt.smpl_model)
         order = torch.randperm(len(dataset)).tolist()       # the reference's shuffled loader, batch 1: drawn before any seed is set
     if opt.pose_sequence is not None:
-        sequence, preprocessor = load_pose_sequence(opt.smpl_model, opt.pose_sequence, device, opt.n_poses)
+        sequence, preprocessor, skeleton = load_pose_sequence(opt.smpl_model, opt.pose_sequence, device, opt.n_poses, return_skeleton=True)
+        if opt.save == "avatar" and not 0 <= opt.avatar_bind_pose < sequence["vertices"].shape[0]:
+            raise ValueError(f"--avatar_bind_pose {opt.avatar_bind_pose}: the sequence has {sequence['vertices'].shape[0]} poses")
         pan, tilt = camera_sweep(opt.n_angles, math.pi / 6, 0, opt.back_and_forth) if sweep_given else (torch.zeros(1), torch.zeros(1))
     for k, seed in enumerate(opt.seeds):
+        if opt.save == "avatar":
+            b = opt.avatar_bind_pose
+            mesh, = generate_textured_meshes(generator, preprocessor, config, seed, {key: v[b:b + 1] for key, v in sequence.items()},
+                                             opt.mesh_resolution, opt.mesh_level, opt.mesh_color_views, opt.mesh_color_range,
+                                             avatar_k=opt.avatar_k)
+            write_glb(os.path.join(out_dir, f"{seed:03d}_avatar.glb"), mesh["rest_vertices"], mesh["faces"], mesh["joints"],
+                      mesh["weights"], skeleton["rest_joints"][b], skeleton["parents"], normals=mesh["rest_normals"],
+                      colors=mesh["colors"], frames=sequence["fk_matrices"], fps=20)
+            continue
         if opt.save == "mesh":
             if opt.pose_sequence is not None:
                 data = sequence

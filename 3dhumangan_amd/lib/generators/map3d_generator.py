@@ -25,7 +25,7 @@ import torch.nn as nn
 
 from ... import _lib
 from ..._stages import stage
-from ..components import smpl
+from ..components import mesh_rig, smpl
 from ..components.isosurface import marching_tetrahedra, vertex_normals
 from ..components.mesh_color import project_colors
 from ..components.ops.bias_act import bias_act
@@ -854,6 +854,29 @@ class Map3DGenerator(nn.Module):
             for b, mesh in enumerate(meshes):
                 mesh["colors"], mesh["coverage"] = self.project_views(mesh, views, frames, b, depth_tolerance, normal_power)
             return meshes
+
+    @torch.no_grad()
+    def extract_avatar(self, latent, conditions, k=4, level=None, views=(), **config):
+        """extract_textured_mesh made re-posable -> its list of dicts, each with the rig entries of mesh_rig.bind added:
+        rest_vertices, rest_normals, joints int32 [V,4], weights [V,4], det [V].
+
+        The generator's own notion of space is "nearest SMPL vertex, then undo that vertex's blended bone transform"
+        (get_geo_features), so the body of `conditions` is the rig: every mesh vertex takes the skin weights of its `k` nearest posed
+        SMPL vertices (conditions["vertices"], ["lbs_weights"]: [B,V,J] or [V,J]), cut to four joints, and goes to the rest pose by
+        the inverse of its blend of conditions["fk_matrices"].  mesh_rig.pose(rest_vertices, joints, weights, fk) puts it into any
+        other pose of the skeleton; with this item's fk_matrices it gives back `vertices`.  `views`, `level` and the config: as in
+        extract_textured_mesh (views=() gives no colours)."""
+        clamp = config.get("clamp_mode", "relu")
+        if clamp != "relu":
+            raise NotImplementedError(f"extract_avatar: clamp_mode={clamp!r} is not supported: only with 'relu' is the raw output of "
+                                      "the density head the density the renderer integrates (above zero)")
+        meshes = self.extract_textured_mesh(latent, conditions, views, level=level, **config)
+        with torch.cuda.device(latent.device):
+            for b, mesh in enumerate(meshes):
+                lbs = conditions["lbs_weights"]
+                mesh.update(mesh_rig.bind(mesh["vertices"], conditions["vertices"][b], lbs[b] if lbs.dim() == 3 else lbs,
+                                          conditions["fk_matrices"][b], normals=mesh["normals"], k=k))
+        return meshes
 
     @staticmethod
     def default_depth_tolerance(config):

@@ -1037,6 +1037,40 @@ int h3d_mesh_project_colors(const float* vertices, const float* normals, int64_t
                             const float* depths, int h, int w, const float* table, float depth_tolerance, int normal_power,
                             float fill, float eps, float* colors, float* coverage, h3d_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * The rig of a mesh (csrc/mesh_rig.hip): the SMPL body's skin carried onto a surface that was extracted in a pose, that surface taken
+ * to the rest pose, and posed again by any transforms of the same skeleton.  No atomics, every sum in a fixed order -- two runs give
+ * bit-identical tensors.  Both selections (K neighbours, four joints) subtract the first value they leave out: a neighbour or a joint
+ * enters and leaves with weight 0, so every output is continuous in the vertex position and no choice is ever undecided -- the
+ * convention of h3d_isosurface_normals and h3d_mesh_project_colors.  All tensors fp32 (joints int32), dense.
+ *
+ * h3d_mesh_bind.  vertices X [M,3] (posed space), normals N [M,3] unit or NULL, smpl_vertices P [V,3] (posed), lbs_weights W [V,J],
+ *   A [J,4,4] (rest -> posed, rows 0..2 used), 1 <= K <= 8, V >= K + 1, 1 <= J <= 64, eps > 0.  Per mesh vertex x:
+ *   1. the K + 1 SMPL vertices of smallest d^2 = (dx dx + dy dy) + dz dz (each operation rounded to fp32, no contraction), ordered by
+ *      (d^2, index);
+ *   2. a_k = 1 / (d_k^2 + eps) - 1 / (d_{K+1}^2 + eps), k = 1..K; s = sum_k a_k in rank order; if s is not finite or s <= 0 (all K + 1
+ *      equidistant) a_k = 1 for the K selected; a^_k = a_k / sum a;
+ *   3. w_j = sum_k a^_k W[i_k, j], the neighbours in rank order;
+ *   4. c = the fifth-largest w_j (with multiplicity), 0 when J < 5; w'_j = max(w_j - c, 0) / sum_j max(w_j - c, 0): at most four are
+ *      non-zero.  joints [M,4] int32 and weights [M,4] fp32 hold them in descending weight, ties by lower joint; a slot with weight 0
+ *      carries joint 0.  Where the sum is zero or not finite (the five largest equal) all four weights are 0 and det says so;
+ *   5. T = sum_j w'_j A_j in ascending joint; R = T[:3,:3], t = T[:3,3];
+ *   6. rest_vertices [M,3] = adj(R) (x - t) / det R;
+ *   7. rest_normals [M,3] = R^T n / |R^T n|, (0,0,0) where that length is zero or not finite; NULL with normals = NULL;
+ *   8. det [M] = det R: where the blend of the bones is close to singular the rest position is not to be trusted.
+ *
+ * h3d_mesh_pose.  rest_vertices [M,3], rest_normals [M,3] or NULL, joints [M,4], weights [M,4], A [n,J,4,4] for n poses ->
+ *   vertices [n,M,3], normals [n,M,3] (NULL with rest_normals = NULL).  T = sum_{i<4} weights_i A[joints_i] in slot order (a joint id
+ *   outside [0, J) is clamped into it); x = R x_r + t; n = sign(det R) cof(R) n_r, normalised with the zero rule above.  Posing a
+ *   freshly bound mesh with the transforms it was bound under gives back X and N up to rounding.
+ *
+ * M = 0 (and n = 0) is valid and launches nothing.  n <= 65535. */
+int h3d_mesh_bind(const float* vertices, const float* normals, int64_t M, const float* smpl_vertices, const float* lbs_weights,
+                  const float* A, int V, int J, int K, float eps, float* rest_vertices, float* rest_normals, int32_t* joints,
+                  float* weights, float* det, h3d_stream_t stream);
+int h3d_mesh_pose(const float* rest_vertices, const float* rest_normals, const int32_t* joints, const float* weights, int64_t M,
+                  const float* A, int n, int J, float* vertices, float* normals, h3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
