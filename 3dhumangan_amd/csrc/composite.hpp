@@ -30,14 +30,24 @@ struct Sample {
 
 // Sample i of z_vals / noise (noise may be null); `last`: the ray's last sample.  ZP / NP are pointer types, so that a caller
 // can pass address-space-1 pointers.  Loads in this order: z, the next z, the noise.
-template <typename ZP, typename NP, typename I>
+// LONG_RAY: alpha from expm1f instead of 1 - expf.  In a thin medium (delta * density ~ 1e-5) the difference keeps a few bits and
+// the device expf rounds with a bias there: the weights' error grows linearly with the sample count, 3.6e-9 per sample
+// (tests/test_gpu_composite_edges.py, thin_lastneg) -- 7e-6 at the 2048 samples the stand-alone kernels accept, under 5e-7 at the
+// sample counts of the fused renders.  The stand-alone integration and its backward take it; the fused renders keep 1 - expf, their
+// outputs are recorded bit for bit (tests/test_gpu_dynamic_tiles.py, test_gpu_ray_head.py).
+template <bool LONG_RAY = false, typename ZP, typename NP, typename I>
 __device__ __forceinline__ Sample composite_sample(float sigma, ZP z_vals, NP noise, I i, bool last, int clamp_mode) {
     Sample s;
     s.z = z_vals[i];
     s.delta = last ? 1e9f : z_vals[i + 1] - s.z;
     s.sg = sigma + (noise ? noise[i] : 0.f);
-    s.e = expf(-s.delta * density(s.sg, clamp_mode));
-    s.alpha = 1.f - s.e;
+    if constexpr (LONG_RAY) {
+        s.alpha = -expm1f(-s.delta * density(s.sg, clamp_mode));
+        s.e = 1.f - s.alpha;                                       // the rounded 1 - alpha: f below is the same expression
+    } else {
+        s.e = expf(-s.delta * density(s.sg, clamp_mode));
+        s.alpha = 1.f - s.e;
+    }
     s.f = (1.f - s.alpha) + 1e-12f;
     return s;
 }

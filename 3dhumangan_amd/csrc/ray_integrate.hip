@@ -32,7 +32,7 @@ __device__ __forceinline__ float scan_weights(const float* __restrict__ sig_base
         const int s = s0 + lane;
         const bool ok = s < S;
         Sample sm;
-        if (ok) sm = composite_sample(sig_base[(int64_t)s * sig_stride], z, noise, s, s == S - 1, clamp_mode);
+        if (ok) sm = composite_sample<true>(sig_base[(int64_t)s * sig_stride], z, noise, s, s == S - 1, clamp_mode);
         const float incl = scan_inclusive<64>(sm.f, lane, 64);
         const float excl = scan_exclusive<64>(incl, lane);
         const float w = sm.alpha * (carry * excl);
@@ -154,12 +154,12 @@ __global__ __launch_bounds__(kThreads) void ray_integrate_scalar(
 extern "C" int h3d_ray_integrate(const float* field, const float* z_vals, const float* noise, float* feats,
                                  float* depth, float* weights, int64_t n_rays, int S, int C, int clamp_mode,
                                  int last_back, int white_back, h3d_stream_t stream) {
-    H3D_REQUIRE(field && z_vals && feats && depth && weights, "h3d_ray_integrate: null pointer");
     H3D_REQUIRE(n_rays >= 0 && n_rays < (int64_t(1) << 31), "h3d_ray_integrate: n_rays=%lld out of range", (long long)n_rays);
     H3D_REQUIRE(S >= 1 && S <= 8192, "h3d_ray_integrate: S=%d must be in [1,8192]", S);
     H3D_REQUIRE(C >= 1, "h3d_ray_integrate: C=%d must be >= 1", C);
     H3D_REQUIRE(clamp_mode == 0 || clamp_mode == 1, "h3d_ray_integrate: clamp_mode must be 0 (relu) or 1 (softplus)");
-    if (n_rays == 0) return H3D_OK;
+    if (n_rays == 0) return H3D_OK;                            // empty tensors have no address: nothing to check, nothing to do
+    H3D_REQUIRE(field && z_vals && feats && depth && weights, "h3d_ray_integrate: null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int NQ = (C + 1) / 4;
     const bool vec = ((C + 1) % 4 == 0) && NQ <= kThreads && h3d::aligned16(field);

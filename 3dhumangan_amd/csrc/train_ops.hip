@@ -175,7 +175,7 @@ __global__ __launch_bounds__(kThreads) void ray_integrate_bwd_kernel(
             Sample sm;
             float da = 0.f;
             if (ok) {
-                sm = composite_sample(blk[(int64_t)s * W + C], z, nz, s, s == S - 1, clamp_mode);
+                sm = composite_sample<true>(blk[(int64_t)s * W + C], z, nz, s, s == S - 1, clamp_mode);
                 da = composite_dalpha(sm, clamp_mode);
             }
             const float incl = scan_inclusive<64>(sm.f, lane, 64);
@@ -335,12 +335,12 @@ extern "C" int h3d_film_sin_bwd(const void* x, const float* freq, const float* p
 extern "C" int h3d_ray_integrate_bwd(const float* field, const float* z_vals, const float* noise, const float* g_feats,
                                      const float* g_depth, const float* g_weights, float* d_field, int64_t n_rays, int S,
                                      int C, int clamp_mode, int last_back, int white_back, h3d_stream_t stream) {
-    H3D_REQUIRE(field && z_vals && g_feats && d_field, "h3d_ray_integrate_bwd: null pointer");
     H3D_REQUIRE(n_rays >= 0 && n_rays < (int64_t(1) << 31), "h3d_ray_integrate_bwd: n_rays=%lld out of range", (long long)n_rays);
     H3D_REQUIRE(S >= 1 && S <= 2048, "h3d_ray_integrate_bwd: S=%d must be in [1,2048]", S);
     H3D_REQUIRE(C >= 1 && C + 1 <= 2048, "h3d_ray_integrate_bwd: C=%d must be in [1,2047]", C);
     H3D_REQUIRE(clamp_mode == 0 || clamp_mode == 1, "h3d_ray_integrate_bwd: clamp_mode must be 0 (relu) or 1 (softplus)");
-    if (n_rays == 0) return H3D_OK;
+    if (n_rays == 0) return H3D_OK;                            // empty tensors have no address: nothing to check, nothing to do
+    H3D_REQUIRE(field && z_vals && g_feats && d_field, "h3d_ray_integrate_bwd: null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t lds = sizeof(float) * (5 * (size_t)S + 4);
     const bool v4 = ((C + 1) % 4 == 0) && h3d::aligned16(field) && h3d::aligned16(d_field);

@@ -41,16 +41,19 @@ def test_ray_integration_golden():
         assert rel_err(w.cpu(), c["weights"]) < 1e-5, k
 
 
-@pytest.mark.parametrize("S,C", [(32, 387), (64, 259), (128, 259), (1, 3), (7, 6), (200, 1027)])
-def test_ray_integration_vs_oracle(S, C):
+# (the relu cases keep the ids they had before the clamp mode became a parameter)
+@pytest.mark.parametrize("S,C,clamp_mode", [pytest.param(S, C, clamp, id=f"{S}-{C}" + ("" if clamp == "relu" else "-" + clamp))
+                                            for clamp in ("relu", "softplus")
+                                            for S, C in [(32, 387), (64, 259), (128, 259), (1, 3), (7, 6), (200, 1027)]])
+def test_ray_integration_vs_oracle(S, C, clamp_mode):
     g = torch.Generator().manual_seed(S * 1000 + C)
     B, R = 2, 37
     field = torch.randn(B, R, S, C + 1, generator=g)
     field[..., -1] = field[..., -1] * 10 - 2
     z = torch.sort(torch.rand(B, R, S, 1, generator=g) + 11.0, dim=2).values
     for last_back in (False, True):
-        ref = O.ray_integration(field.double(), z.double(), None, "relu", last_back, True)
-        got = vr.ray_integration(dev(field), dev(z), noise_std=0, clamp_mode="relu", last_back=last_back,
+        ref = O.ray_integration(field.double(), z.double(), None, clamp_mode, last_back, True)
+        got = vr.ray_integration(dev(field), dev(z), noise_std=0, clamp_mode=clamp_mode, last_back=last_back,
                                  white_back=True)
         for a, b, name in zip(got, ref, ("feats", "depth", "weights")):
             assert rel_err(a.cpu(), b) < 2e-5, (name, last_back)
