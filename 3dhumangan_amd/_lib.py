@@ -170,6 +170,7 @@ _SIGNATURES = {
     "h3d_isosurface_emit": (C.c_int, [_p, _i, _i, _i, _f, C.POINTER(_f), C.POINTER(_f), _p, _p, _p, _l, _p, _l, _p]),
     "h3d_isosurface_normals": (C.c_int, [_p, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _p, _l, _p, _p, _p]),
     "h3d_mesh_project_colors": (C.c_int, [_p, _p, _l, _p, _i, _i, _i, _p, _i, _i, _p, _f, _i, _f, _f, _p, _p, _p]),
+    "h3d_mesh_bake_texture": (C.c_int, [_p, _p, _l, _p, _l, _i, _p, _i, _i, _i, _p, _i, _i, _p, _f, _i, _f, _f, _p, _p, _p]),
     "h3d_mesh_bind": (C.c_int, [_p, _p, _l, _p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p]),
     "h3d_mesh_pose": (C.c_int, [_p, _p, _p, _p, _l, _p, _i, _i, _p, _p, _p]),
 }

@@ -26,6 +26,10 @@ view sees stays at colour 0 (mid grey).  With random-init weights the frames are
 `--avatar_bind_pose` of the sequence, takes the SMPL body's skin weights from its `--avatar_k` nearest body vertices and goes to the
 rest pose (Map3DGenerator.extract_avatar); the file holds the rest mesh with normals (colours with `--mesh_color_views`), the skin, the
 skeleton and every pose of the sequence as a key of one animation -- a viewer plays the motion without the network.
+`--mesh_texture S` (with `--mesh_color_views K`, K >= 1) bakes the same K frames into an S x S texture atlas
+(Map3DGenerator.bake_views): the avatar's `.glb` then carries the texture instead of vertex colours, and `--save mesh` writes, beside
+each `.ply` (unchanged), a static `.glb` of the same stem with the texture -- the appearance then has the resolution of the frames,
+whatever `--mesh_resolution` is.
 
     python -m 3dhumangan_amd.apps.sample_from_generator --config MAP3DBN --seeds 1 2 --n_angles 8 --save png
 """
@@ -170,12 +174,13 @@ def generate_meshes(generator, config, seed, conditions, resolution, level=None)
 
 @torch.no_grad()
 def generate_textured_meshes(generator, preprocessor, config, seed, conditions, resolution, level=None, n_views=0, view_range=30.0,
-                             avatar_k=None):
+                             avatar_k=None, texture_size=0):
     """generate_meshes with normals and, for n_views > 0, colours -> list of dict(vertices, faces, normals, colors, coverage).
     avatar_k: the meshes come from Map3DGenerator.extract_avatar(k=avatar_k) and carry its rig entries as well.
     The colours come from `n_views` frames panned evenly over +-view_range degrees (one view: angle 0), each made as
     generate_pose_frames makes a frame -- RNGs seeded anew, the latent drawn, the conditions turned by the preprocessor, staged_forward
-    -- so the view at angle 0 is the frame the app saves for this seed and pose."""
+    -- so the view at angle 0 is the frame the app saves for this seed and pose.  texture_size > 0 (with views): the dicts carry
+    uvs, texture and texture_coverage as well, baked from the same frames."""
     dev = generator.device
     pan = torch.linspace(-math.radians(view_range), math.radians(view_range), n_views) if n_views > 1 else torch.zeros(n_views)
     meshes = []
@@ -196,6 +201,8 @@ def generate_textured_meshes(generator, preprocessor, config, seed, conditions, 
             frames.append(generator.mesh_view(z, views[-1], **config))
         if views:
             mesh["colors"], mesh["coverage"] = generator.project_views(mesh, views, frames, 0, generator.default_depth_tolerance(config))
+            if texture_size:
+                mesh.update(generator.bake_views(mesh, views, frames, 0, generator.default_depth_tolerance(config), texture_size))
         meshes.append(mesh)
     return meshes
 
@@ -242,6 +249,8 @@ def build_parser():
     ap.add_argument("--mesh_color_views", type=int, default=0, help="--save mesh: colour the vertices from this many frames "
                     "panned evenly over +-mesh_color_range (red green blue; implies --mesh_normals)")
     ap.add_argument("--mesh_color_range", type=float, default=30.0, help="--mesh_color_views: half-width of the pan in degrees")
+    ap.add_argument("--mesh_texture", type=int, default=0, help="--save mesh / avatar: bake the --mesh_color_views frames into a "
+                    "texture atlas of this many texels a side, written into the .glb (0: none)")
     ap.add_argument("--avatar_k", type=int, default=4, help="--save avatar: body vertices (1..8) whose skin weights a mesh vertex blends")
     ap.add_argument("--avatar_bind_pose", type=int, default=0, help="--save avatar: the pose of the sequence at which the mesh is "
                     "extracted and bound; every pose becomes a key of the file's animation")
@@ -258,7 +267,14 @@ def build_parser():
 
 
 def main(argv=None):
-    opt = build_parser().parse_args(argv)
+    parser = build_parser()
+    opt = parser.parse_args(argv)
+    if opt.mesh_texture < 0:
+        parser.error(f"--mesh_texture {opt.mesh_texture}: the texture's edge in texels, 0 for none")
+    if opt.mesh_texture and opt.mesh_color_views < 1:
+        parser.error("--mesh_texture needs the frames it is baked from: pass --mesh_color_views K with K >= 1")
+    if opt.mesh_texture and opt.save not in ("mesh", "avatar"):
+        parser.error("--mesh_texture goes with --save mesh or --save avatar")
     sweep_given = opt.n_angles is not None
     if opt.n_angles is None:
         opt.n_angles = 40
@@ -313,10 +329,11 @@ def main(argv=None):
             b = opt.avatar_bind_pose
             mesh, = generate_textured_meshes(generator, preprocessor, config, seed, {key: v[b:b + 1] for key, v in sequence.items()},
                                              opt.mesh_resolution, opt.mesh_level, opt.mesh_color_views, opt.mesh_color_range,
-                                             avatar_k=opt.avatar_k)
+                                             avatar_k=opt.avatar_k, texture_size=opt.mesh_texture)
+            look = dict(uvs=mesh["uvs"], texture=mesh["texture"]) if opt.mesh_texture else dict(colors=mesh["colors"])
             write_glb(os.path.join(out_dir, f"{seed:03d}_avatar.glb"), mesh["rest_vertices"], mesh["faces"], mesh["joints"],
                       mesh["weights"], skeleton["rest_joints"][b], skeleton["parents"], normals=mesh["rest_normals"],
-                      colors=mesh["colors"], frames=sequence["fk_matrices"], fps=20)
+                      frames=sequence["fk_matrices"], fps=20, **look)
             continue
         if opt.save == "mesh":
             if opt.pose_sequence is not None:
@@ -327,13 +344,18 @@ def main(argv=None):
                 data = record if opt.smpl_record is not None else synthetic.make_conditions(1, 6890, seed=seed)
             if opt.mesh_normals or opt.mesh_color_views:
                 meshes = generate_textured_meshes(generator, preprocessor, config, seed, data, opt.mesh_resolution, opt.mesh_level,
-                                                  opt.mesh_color_views, opt.mesh_color_range)
+                                                  opt.mesh_color_views, opt.mesh_color_range, texture_size=opt.mesh_texture)
+                textured = meshes
                 meshes = [(m["vertices"], m["faces"], m["normals"], m["colors"]) for m in meshes]
             else:
                 meshes = generate_meshes(generator, config, seed, data, opt.mesh_resolution, opt.mesh_level)
             for i, mesh in enumerate(meshes):
                 name = f"{seed:03d}_mesh_{i:03d}.ply" if opt.pose_sequence is not None else f"{seed:03d}_mesh.ply"
                 write_ply(os.path.join(out_dir, name), *mesh)
+                if opt.mesh_texture:
+                    m = textured[i]
+                    write_glb(os.path.join(out_dir, name[:-4] + ".glb"), m["vertices"], m["faces"], normals=m["normals"], uvs=m["uvs"],
+                              texture=m["texture"])
             continue
         if opt.pose_sequence is not None:
             frames, semantics = generate_pose_frames(generator, preprocessor, config, seed, sequence, pan, tilt)

@@ -13,6 +13,10 @@
 //
 // Colours: the views run in a loop; the per-view camera table (12 world-to-camera entries, the origin, the focal) is read at a
 // wave-uniform index, i.e. through the scalar cache.  Each view costs a vertex 4 depth and 12 image texels.
+//
+// Texture (h3d_mesh_bake_texture): the same per-point colour at every texel of an atlas that gives each triangle half of a square
+// cell; one thread per texel, a wave on an 8 x 8 texel block.  Face indices are clamped into the vertex range before they address
+// memory; every store is guarded by the texture's edge.
 #include "common.hpp"
 
 namespace {
@@ -132,22 +136,16 @@ __device__ inline float bilinear_at(const float* __restrict__ plane, int cols, i
     return lerp(lerp(r0[x0], r0[x1], ax), lerp(r1[x0], r1[x1], ax), ay);
 }
 
-__global__ __launch_bounds__(kThreads) void mesh_project_colors_kernel(const float* __restrict__ vertices,
-                                                                       const float* __restrict__ normals, int64_t V,
-                                                                       const float* __restrict__ images,
-                                                                       const float* __restrict__ depths,
-                                                                       const float* __restrict__ table, Views s,
-                                                                       float depth_tolerance, int normal_power, float fill, float eps,
-                                                                       float* __restrict__ colors, float* __restrict__ coverage) {
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= V) return;
-    const float px = vertices[i * 3 + 0], py = vertices[i * 3 + 1], pz = vertices[i * 3 + 2];
-    const float nx = normals[i * 3 + 0], ny = normals[i * 3 + 1], nz = normals[i * 3 + 2];
+// The K views of one surface point (position p, normal n): sum = sum_k w_k and the w_k-weighted colour sums, the views in
+// ascending k -- the definition of h3d_mesh_project_colors, shared by the per-vertex and the per-texel kernel.
+__device__ inline void blend_views(float px, float py, float pz, float nx, float ny, float nz, const float* __restrict__ images,
+                                   const float* __restrict__ depths, const float* __restrict__ table, const Views& s,
+                                   float depth_tolerance, int normal_power, float& sum, float& r, float& g, float& b) {
     const float span = (float)s.w / (float)s.h;
     const float wm = (float)(s.w - 1), hm = (float)(s.h - 1);
     const float ratio_x = (float)s.W / (float)s.w, ratio_y = (float)s.H / (float)s.h;
     const size_t plane = (size_t)s.H * s.W;
-    float sum = 0.f, r = 0.f, g = 0.f, b = 0.f;
+    sum = 0.f, r = 0.f, g = 0.f, b = 0.f;
     for (int k = 0; k < s.K; ++k) {
         const float* __restrict__ M = table + (size_t)k * 16;           // wave-uniform
         const float cx = M[0] * px + M[1] * py + M[2] * pz + M[3];
@@ -177,11 +175,78 @@ __global__ __launch_bounds__(kThreads) void mesh_project_colors_kernel(const flo
         g += wk * bilinear_at(im + plane, s.W, x0, x1, y0, y1, ax, ay);
         b += wk * bilinear_at(im + 2 * plane, s.W, x0, x1, y0, y1, ax, ay);
     }
+}
+
+__global__ __launch_bounds__(kThreads) void mesh_project_colors_kernel(const float* __restrict__ vertices,
+                                                                       const float* __restrict__ normals, int64_t V,
+                                                                       const float* __restrict__ images,
+                                                                       const float* __restrict__ depths,
+                                                                       const float* __restrict__ table, Views s,
+                                                                       float depth_tolerance, int normal_power, float fill, float eps,
+                                                                       float* __restrict__ colors, float* __restrict__ coverage) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= V) return;
+    const float px = vertices[i * 3 + 0], py = vertices[i * 3 + 1], pz = vertices[i * 3 + 2];
+    const float nx = normals[i * 3 + 0], ny = normals[i * 3 + 1], nz = normals[i * 3 + 2];
+    float sum, r, g, b;
+    blend_views(px, py, pz, nx, ny, nz, images, depths, table, s, depth_tolerance, normal_power, sum, r, g, b);
     const float den = sum + eps, back = eps * fill;
     colors[i * 3 + 0] = (r + back) / den;
     colors[i * 3 + 1] = (g + back) / den;
     colors[i * 3 + 2] = (b + back) / den;
     coverage[i] = sum;
+}
+
+struct Atlas {
+    int S, R, c;                                           // texture edge, cells per row, cell edge in texels
+};
+
+// One thread per texel; a wave covers an 8 x 8 texel block (a workgroup 16 x 16), so it sees one to four triangles and their nine
+// vertex / normal loads are shared through L1.  Every face index is clamped into [0, V - 1]; every store is guarded by S.
+__global__ __launch_bounds__(kThreads) void mesh_bake_texture_kernel(const float* __restrict__ vertices,
+                                                                     const float* __restrict__ normals, int64_t V,
+                                                                     const int32_t* __restrict__ faces, int64_t T, Atlas a,
+                                                                     const float* __restrict__ images,
+                                                                     const float* __restrict__ depths,
+                                                                     const float* __restrict__ table, Views s,
+                                                                     float depth_tolerance, int normal_power, float fill, float eps,
+                                                                     float* __restrict__ texture, float* __restrict__ coverage) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int q = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);                  // column
+    const int row = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (q >= a.S || row >= a.S) return;
+    const int cy = row / a.c, cx = q / a.c;
+    const int j = row - cy * a.c, i = q - cx * a.c;
+    const bool upper = i + j >= a.c - 1;
+    const int64_t t = 2 * ((int64_t)cy * a.R + cx) + (upper ? 1 : 0);
+    const size_t texel = (size_t)row * a.S + q;
+    float sum = 0.f, r = 0.f, g = 0.f, b = 0.f;
+    float den = 1.f, back = fill;                          // an unowned texel: the fill colour itself, coverage 0
+    if (cy < a.R && cx < a.R && t < T) {
+        const int ii = upper ? a.c - 1 - i : i, jj = upper ? a.c - 1 - j : j;
+        const float m = (float)(a.c - 3);
+        const float b1 = (float)ii / m, b2 = (float)jj / m;
+        const float b0 = 1.f - b1 - b2;
+        const int64_t top = V - 1;
+        const int64_t i0 = min(max((int64_t)faces[t * 3 + 0], (int64_t)0), top) * 3;
+        const int64_t i1 = min(max((int64_t)faces[t * 3 + 1], (int64_t)0), top) * 3;
+        const int64_t i2 = min(max((int64_t)faces[t * 3 + 2], (int64_t)0), top) * 3;
+        const float px = b0 * vertices[i0 + 0] + b1 * vertices[i1 + 0] + b2 * vertices[i2 + 0];
+        const float py = b0 * vertices[i0 + 1] + b1 * vertices[i1 + 1] + b2 * vertices[i2 + 1];
+        const float pz = b0 * vertices[i0 + 2] + b1 * vertices[i1 + 2] + b2 * vertices[i2 + 2];
+        float nx = b0 * normals[i0 + 0] + b1 * normals[i1 + 0] + b2 * normals[i2 + 0];
+        float ny = b0 * normals[i0 + 1] + b1 * normals[i1 + 1] + b2 * normals[i2 + 1];
+        float nz = b0 * normals[i0 + 2] + b1 * normals[i1 + 2] + b2 * normals[i2 + 2];
+        const float len = sqrtf(nx * nx + ny * ny + nz * nz);
+        if (len > 0.f && is_finite(len)) nx /= len, ny /= len, nz /= len;
+        else nx = ny = nz = 0.f;
+        blend_views(px, py, pz, nx, ny, nz, images, depths, table, s, depth_tolerance, normal_power, sum, r, g, b);
+        den = sum + eps, back = eps * fill;
+    }
+    texture[texel * 3 + 0] = (r + back) / den;
+    texture[texel * 3 + 1] = (g + back) / den;
+    texture[texel * 3 + 2] = (b + back) / den;
+    coverage[texel] = sum;
 }
 
 bool positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }
@@ -227,4 +292,41 @@ extern "C" int h3d_mesh_project_colors(const float* vertices, const float* norma
                        static_cast<hipStream_t>(stream), vertices, normals, V, images, depths, table, Views{K, H, W, h, w},
                        depth_tolerance, normal_power, fill, eps, colors, coverage);
     return h3d::launch_status("h3d_mesh_project_colors");
+}
+
+extern "C" int h3d_mesh_bake_texture(const float* vertices, const float* normals, int64_t V, const int32_t* faces, int64_t T, int S,
+                                     const float* images, int K, int H, int W, const float* depths, int h, int w, const float* table,
+                                     float depth_tolerance, int normal_power, float fill, float eps, float* texture, float* coverage,
+                                     h3d_stream_t stream) {
+    H3D_REQUIRE(S >= 2 && S <= 8192, "h3d_mesh_bake_texture: S=%d outside 2..8192", S);
+    H3D_REQUIRE(T >= 0 && T <= 2 * (int64_t)2048 * 2048, "h3d_mesh_bake_texture: T=%lld out of range", (long long)T);
+    const int64_t cells = (T + 1) / 2;
+    int R = 1;                                             // ceil(sqrt(cells)) = isqrt(cells - 1) + 1 in integers
+    if (cells > 1) {
+        int64_t root = (int64_t)sqrt((double)(cells - 1));
+        while (root * root > cells - 1) --root;
+        while ((root + 1) * (root + 1) <= cells - 1) ++root;
+        R = (int)root + 1;
+    }
+    const int c = S / R;
+    H3D_REQUIRE(c >= 4, "h3d_mesh_bake_texture: T=%lld triangles need a texture of at least %d texels a side (cells of 4), got S=%d",
+                (long long)T, 4 * R, S);
+    H3D_REQUIRE(K >= 1, "h3d_mesh_bake_texture: K=%d views (at least 1)", K);
+    H3D_REQUIRE(H >= 2 && W >= 2 && h >= 2 && w >= 2, "h3d_mesh_bake_texture: images %dx%d and depths %dx%d need at least 2x2", H, W,
+                h, w);
+    H3D_REQUIRE((int64_t)K * 3 * H * W < ((int64_t)1 << 40) && (int64_t)K * h * w < ((int64_t)1 << 40),
+                "h3d_mesh_bake_texture: views too large");
+    H3D_REQUIRE(positive_finite(depth_tolerance), "h3d_mesh_bake_texture: depth_tolerance=%g must be positive", depth_tolerance);
+    H3D_REQUIRE(positive_finite(eps), "h3d_mesh_bake_texture: eps=%g must be positive", eps);
+    H3D_REQUIRE(normal_power >= 1 && normal_power <= 8, "h3d_mesh_bake_texture: normal_power=%d outside 1..8", normal_power);
+    H3D_REQUIRE(V >= 0 && V < ((int64_t)1 << 31), "h3d_mesh_bake_texture: V=%lld out of range", (long long)V);
+    H3D_REQUIRE(T == 0 || V >= 1, "h3d_mesh_bake_texture: %lld triangles without a vertex", (long long)T);
+    H3D_REQUIRE(texture && coverage, "h3d_mesh_bake_texture: null pointer");
+    H3D_REQUIRE(T == 0 || (vertices && normals && faces && images && depths && table), "h3d_mesh_bake_texture: null pointer");
+    h3d::pre_launch();
+    const unsigned blocks = (unsigned)((S + 15) / 16);
+    hipLaunchKernelGGL(mesh_bake_texture_kernel, dim3(blocks, blocks), dim3(kThreads), 0, static_cast<hipStream_t>(stream), vertices,
+                       normals, V, faces, T, Atlas{S, R, c}, images, depths, table, Views{K, H, W, h, w}, depth_tolerance, normal_power,
+                       fill, eps, texture, coverage);
+    return h3d::launch_status("h3d_mesh_bake_texture");
 }

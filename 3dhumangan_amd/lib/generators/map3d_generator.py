@@ -28,6 +28,7 @@ from ..._stages import stage
 from ..components import mesh_rig, smpl
 from ..components.isosurface import marching_tetrahedra, vertex_normals
 from ..components.mesh_color import project_colors
+from ..components.mesh_texture import atlas_uvs, bake_texture
 from ..components.ops.bias_act import bias_act
 from . import volume_rendering as vr
 from .differentiable import synthesis_forward
@@ -815,7 +816,8 @@ class Map3DGenerator(nn.Module):
             return [marching_tetrahedra(sigma[b], level, o, s) for b, (o, s) in enumerate(zip(origin.tolist(), spacing.tolist()))]
 
     @torch.no_grad()
-    def extract_textured_mesh(self, latent, conditions, views, level=None, depth_tolerance=None, normal_power=2, **config):
+    def extract_textured_mesh(self, latent, conditions, views, level=None, depth_tolerance=None, normal_power=2, texture_size=None,
+                              **config):
         """extract_mesh with per-vertex attributes -> one dict(vertices, faces, normals, colors, coverage) per item.
 
         vertices and faces are extract_mesh's; normals are vertex_normals of the same density grid (one density_grid call serves
@@ -827,7 +829,11 @@ class Map3DGenerator(nn.Module):
         weighs the views at every vertex: colors fp32 [V,3] in the images' [-1, 1], coverage fp32 [V] = how much the vertex was seen
         (a vertex no view sees has coverage 0 and colour 0).  views=[] gives colors = coverage = None.
         depth_tolerance=None: 2 * (ray_end - ray_start) / num_steps, two coarse steps of the render -- the resolution to which its
-        expected depth and the iso-surface can agree."""
+        expected depth and the iso-surface can agree.
+        texture_size=S (needs at least one view): every dict gains uvs fp32 [T,3,2] (per face corner, v = 0 at the top row), texture
+        fp32 [S,S,3] and texture_coverage fp32 [S,S] -- the same frames baked into a texture atlas (lib/components/mesh_texture.py),
+        so the appearance has the resolution of the texture, not of the density grid.  Nothing else is rendered or drawn for it, and
+        colors / coverage are what they are without it."""
         clamp = config.get("clamp_mode", "relu")
         if clamp != "relu":
             raise NotImplementedError(f"extract_textured_mesh: clamp_mode={clamp!r} is not supported: only with 'relu' is the raw output "
@@ -835,6 +841,8 @@ class Map3DGenerator(nn.Module):
         if int(normal_power) != normal_power or not 1 <= int(normal_power) <= 8:
             raise ValueError(f"extract_textured_mesh: normal_power={normal_power} must be an integer 1..8")
         views = list(views)
+        if texture_size is not None and not views:
+            raise ValueError("extract_textured_mesh: texture_size needs at least one view to bake the texture from")
         if level is None:
             level = math.log(2.0) * config.get("num_steps", 24) / (config["ray_end"] - config["ray_start"])
         if depth_tolerance is None:
@@ -853,10 +861,12 @@ class Map3DGenerator(nn.Module):
             frames = [self.mesh_view(latent, view, **config) for view in views]
             for b, mesh in enumerate(meshes):
                 mesh["colors"], mesh["coverage"] = self.project_views(mesh, views, frames, b, depth_tolerance, normal_power)
+                if texture_size is not None:
+                    mesh.update(self.bake_views(mesh, views, frames, b, depth_tolerance, texture_size, normal_power))
             return meshes
 
     @torch.no_grad()
-    def extract_avatar(self, latent, conditions, k=4, level=None, views=(), **config):
+    def extract_avatar(self, latent, conditions, k=4, level=None, views=(), texture_size=None, **config):
         """extract_textured_mesh made re-posable -> its list of dicts, each with the rig entries of mesh_rig.bind added:
         rest_vertices, rest_normals, joints int32 [V,4], weights [V,4], det [V].
 
@@ -865,12 +875,13 @@ class Map3DGenerator(nn.Module):
         SMPL vertices (conditions["vertices"], ["lbs_weights"]: [B,V,J] or [V,J]), cut to four joints, and goes to the rest pose by
         the inverse of its blend of conditions["fk_matrices"].  mesh_rig.pose(rest_vertices, joints, weights, fk) puts it into any
         other pose of the skeleton; with this item's fk_matrices it gives back `vertices`.  `views`, `level` and the config: as in
-        extract_textured_mesh (views=() gives no colours)."""
+        extract_textured_mesh (views=() gives no colours).  texture_size: as there; the UVs belong to the faces, so the texture baked
+        in the posed space serves the rest mesh unchanged."""
         clamp = config.get("clamp_mode", "relu")
         if clamp != "relu":
             raise NotImplementedError(f"extract_avatar: clamp_mode={clamp!r} is not supported: only with 'relu' is the raw output of "
                                       "the density head the density the renderer integrates (above zero)")
-        meshes = self.extract_textured_mesh(latent, conditions, views, level=level, **config)
+        meshes = self.extract_textured_mesh(latent, conditions, views, level=level, texture_size=texture_size, **config)
         with torch.cuda.device(latent.device):
             for b, mesh in enumerate(meshes):
                 lbs = conditions["lbs_weights"]
@@ -894,9 +905,22 @@ class Map3DGenerator(nn.Module):
         return out["rgbs"].float().clamp(-1, 1), out["depths"][:, 0].float() * (config["depth_length"] / 2.0) + zc.view(-1, 1, 1)
 
     @staticmethod
+    def _view_tensors(views, frames, b):
+        """item `b` of every view (conditions dicts) and its mesh_view frame, stacked -> (images, depths, focals, scales, cam2world)"""
+        return (torch.stack([im[b] for im, _ in frames]), torch.stack([d[b] for _, d in frames]),
+                torch.stack([v["intrinsics"][b, 0, 0] for v in views]).float(), torch.stack([v["scales"][b] for v in views]).float(),
+                torch.stack([v["cam2world_matrices"][b] for v in views]).float())
+
+    @staticmethod
     def project_views(mesh, views, frames, b, depth_tolerance, normal_power=2):
         """project_colors of item `b` of every view (conditions dicts) and its mesh_view frame onto `mesh` -> (colors, coverage)"""
-        return project_colors(mesh["vertices"], mesh["normals"], torch.stack([im[b] for im, _ in frames]),
-                              torch.stack([d[b] for _, d in frames]), torch.stack([v["intrinsics"][b, 0, 0] for v in views]).float(),
-                              torch.stack([v["scales"][b] for v in views]).float(),
-                              torch.stack([v["cam2world_matrices"][b] for v in views]).float(), depth_tolerance, normal_power)
+        return project_colors(mesh["vertices"], mesh["normals"], *Map3DGenerator._view_tensors(views, frames, b), depth_tolerance,
+                              normal_power)
+
+    @staticmethod
+    def bake_views(mesh, views, frames, b, depth_tolerance, texture_size, normal_power=2):
+        """bake_texture of the same views and frames as project_views -> dict(uvs [T,3,2], texture [S,S,3], texture_coverage [S,S])"""
+        texture, coverage = bake_texture(mesh["vertices"], mesh["faces"], mesh["normals"], *Map3DGenerator._view_tensors(views, frames, b),
+                                         depth_tolerance, texture_size, normal_power)
+        uvs = torch.from_numpy(atlas_uvs(mesh["faces"].shape[0], texture_size)).to(texture.device)
+        return {"uvs": uvs, "texture": texture, "texture_coverage": coverage}

@@ -1037,6 +1037,28 @@ int h3d_mesh_project_colors(const float* vertices, const float* normals, int64_t
                             const float* depths, int h, int w, const float* table, float depth_tolerance, int normal_power,
                             float fill, float eps, float* colors, float* coverage, h3d_stream_t stream);
 
+/* h3d_mesh_bake_texture: the colour of h3d_mesh_project_colors at every texel of a texture atlas, so that the appearance has the
+ * resolution of the frames and not of the mesh.  vertices, normals [V,3] fp32, faces [T,3] int32, texture [S,S,3] fp32 and coverage
+ * [S,S] fp32 (row 0 is the top row); images, depths, table and the four constants: as above.
+ *   Layout (integers): cells = ceil(T / 2), R = ceil(sqrt(cells)) = isqrt(cells - 1) + 1 (R = 1 for T = 0), cell edge c = S / R
+ *   (floor), m = c - 3; c >= 4 is required (S >= 4 R).  Triangle t lies in cell t / 2 (cell k at row k / R, column k % R, origin
+ *   (x0, y0) = (c (k % R), c (k / R))), the even one in the lower-left half.  Texel (row r, column q): cy = r / c, cx = q / c, valid
+ *   iff both < R; j = r % c, i = q % c, upper = (i + j >= c - 1), t = 2 (cy R + cx) + upper; the texel is owned iff valid and t < T.
+ *   (ii, jj) = upper ? (c - 1 - i, c - 1 - j) : (i, j); b1 = ii / m, b2 = jj / m, b0 = 1 - b1 - b2 (fp32, in this order), not
+ *   clamped: the diagonals i + j in {c - 2, c - 1, c} are the gutter and hold the affine continuation of their triangle.
+ *   Corner UVs in texel units (divided by S; v = 0 is the top row): even t (x0 + .5, y0 + .5), (x0 + m + .5, y0 + .5),
+ *   (x0 + .5, y0 + m + .5); odd t (x0 + c - .5, y0 + c - .5), (x0 + 2.5, y0 + c - .5), (x0 + c - .5, y0 + 2.5).  Corner texels
+ *   carry one-hot barycentrics, and the bilinear footprint of a point inside a UV triangle touches texels of that triangle only.
+ *   Per owned texel: the three face indices clamped into [0, V - 1] (a wrong index gives a wrong texel, never a load out of
+ *   range); x = b0 v0 + b1 v1 + b2 v2; n = (b0 n0 + b1 n1 + b2 n2) / |.|, (0,0,0) where that length is zero or not finite; then
+ *   w_k, c_k, coverage and colour exactly as h3d_mesh_project_colors defines them at (x, n).  An unowned texel has colour `fill` and
+ *   coverage 0.  One thread per texel, a wave on an 8 x 8 texel block; no atomics, two runs give the same bits.
+ *   2 <= S <= 8192; T = 0 is valid (everything is `fill`); V >= 1 when T >= 1. */
+int h3d_mesh_bake_texture(const float* vertices, const float* normals, int64_t V, const int32_t* faces, int64_t T, int S,
+                          const float* images, int K, int H, int W, const float* depths, int h, int w, const float* table,
+                          float depth_tolerance, int normal_power, float fill, float eps, float* texture, float* coverage,
+                          h3d_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * The rig of a mesh (csrc/mesh_rig.hip): the SMPL body's skin carried onto a surface that was extracted in a pose, that surface taken
  * to the rest pose, and posed again by any transforms of the same skeleton.  No atomics, every sum in a fixed order -- two runs give
