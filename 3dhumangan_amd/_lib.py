@@ -173,6 +173,9 @@ _SIGNATURES = {
     "h3d_mesh_bake_texture": (C.c_int, [_p, _p, _l, _p, _l, _i, _p, _i, _i, _i, _p, _i, _i, _p, _f, _i, _f, _f, _p, _p, _p]),
     "h3d_mesh_bind": (C.c_int, [_p, _p, _l, _p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p]),
     "h3d_mesh_pose": (C.c_int, [_p, _p, _p, _p, _l, _p, _i, _i, _p, _p, _p]),
+    "h3d_mesh_cluster_cells": (C.c_int, [_p, _l, C.POINTER(_f), _f, _i, _i, _i, _p, _p]),
+    "h3d_mesh_cluster_faces": (C.c_int, [_p, _l, _p, _l, _p, _p, _p, _p]),
+    "h3d_mesh_cluster_solve": (C.c_int, [_p, _l, _p, _l, _p, _p, _p, _p, _p, _l, C.POINTER(_f), _f, _i, _i, _i, _f, _f, _p, _p]),
 }
 
 

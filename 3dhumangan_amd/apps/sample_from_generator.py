@@ -29,7 +29,9 @@ skeleton and every pose of the sequence as a key of one animation -- a viewer pl
 `--mesh_texture S` (with `--mesh_color_views K`, K >= 1) bakes the same K frames into an S x S texture atlas
 (Map3DGenerator.bake_views): the avatar's `.glb` then carries the texture instead of vertex colours, and `--save mesh` writes, beside
 each `.ply` (unchanged), a static `.glb` of the same stem with the texture -- the appearance then has the resolution of the frames,
-whatever `--mesh_resolution` is.
+whatever `--mesh_resolution` is.  `--mesh_simplify K` (with `--save mesh` / `--save avatar`) reduces every surface by quadric vertex
+clustering on cells of K voxels of the density grid (Map3DGenerator.extract_mesh(simplify=K)) before anything else is computed on it:
+fewer triangles of the same shape, and a larger cell of the atlas for each.
 
     python -m 3dhumangan_amd.apps.sample_from_generator --config MAP3DBN --seeds 1 2 --n_angles 8 --save png
 """
@@ -160,27 +162,29 @@ def load_smpl_record(path, dev):
 
 
 @torch.no_grad()
-def generate_meshes(generator, config, seed, conditions, resolution, level=None):
+def generate_meshes(generator, config, seed, conditions, resolution, level=None, simplify=None):
     """The surface of every item of the batched `conditions` for the latent of `seed` -> list of (vertices, faces).  The RNGs are
-    seeded anew per item, as generate_pose_frames does per frame: a mesh belongs to the frame of the same seed and pose."""
+    seeded anew per item, as generate_pose_frames does per frame: a mesh belongs to the frame of the same seed and pose.
+    simplify: Map3DGenerator.extract_mesh's (the cluster cell in voxels, None: off)."""
     dev = generator.device
     meshes = []
     for i in range(conditions["vertices"].shape[0]):
         z = latent_for_seed(seed, config["latent_dim"]).to(dev)
         body = {k: conditions[k][i:i + 1].to(dev) for k in generator.MESH_CONDITIONS}
-        meshes += generator.extract_mesh(z, body, level=level, resolution=resolution, **config)
+        meshes += generator.extract_mesh(z, body, level=level, resolution=resolution, simplify=simplify, **config)
     return meshes
 
 
 @torch.no_grad()
 def generate_textured_meshes(generator, preprocessor, config, seed, conditions, resolution, level=None, n_views=0, view_range=30.0,
-                             avatar_k=None, texture_size=0):
+                             avatar_k=None, texture_size=0, simplify=None):
     """generate_meshes with normals and, for n_views > 0, colours -> list of dict(vertices, faces, normals, colors, coverage).
     avatar_k: the meshes come from Map3DGenerator.extract_avatar(k=avatar_k) and carry its rig entries as well.
     The colours come from `n_views` frames panned evenly over +-view_range degrees (one view: angle 0), each made as
     generate_pose_frames makes a frame -- RNGs seeded anew, the latent drawn, the conditions turned by the preprocessor, staged_forward
     -- so the view at angle 0 is the frame the app saves for this seed and pose.  texture_size > 0 (with views): the dicts carry
-    uvs, texture and texture_coverage as well, baked from the same frames."""
+    uvs, texture and texture_coverage as well, baked from the same frames.  simplify: as in generate_meshes; normals, rig, colours
+    and texture belong to the simplified mesh."""
     dev = generator.device
     pan = torch.linspace(-math.radians(view_range), math.radians(view_range), n_views) if n_views > 1 else torch.zeros(n_views)
     meshes = []
@@ -190,9 +194,9 @@ def generate_textured_meshes(generator, preprocessor, config, seed, conditions, 
         base["scales"] = base["scales"].reshape(1)
         body = {k: base[k] for k in generator.MESH_CONDITIONS}
         if avatar_k is None:
-            mesh, = generator.extract_textured_mesh(z, body, [], level=level, resolution=resolution, **config)
+            mesh, = generator.extract_textured_mesh(z, body, [], level=level, resolution=resolution, simplify=simplify, **config)
         else:
-            mesh, = generator.extract_avatar(z, body, k=avatar_k, level=level, resolution=resolution, **config)
+            mesh, = generator.extract_avatar(z, body, k=avatar_k, level=level, resolution=resolution, simplify=simplify, **config)
         views, frames = [], []
         for a_h in pan.to(dev):
             z = latent_for_seed(seed, config["latent_dim"]).to(dev)
@@ -251,6 +255,8 @@ def build_parser():
     ap.add_argument("--mesh_color_range", type=float, default=30.0, help="--mesh_color_views: half-width of the pan in degrees")
     ap.add_argument("--mesh_texture", type=int, default=0, help="--save mesh / avatar: bake the --mesh_color_views frames into a "
                     "texture atlas of this many texels a side, written into the .glb (0: none)")
+    ap.add_argument("--mesh_simplify", type=float, default=0.0, help="--save mesh / avatar: reduce the surface by quadric vertex "
+                    "clustering on cells of this many voxels of the density grid (0: off)")
     ap.add_argument("--avatar_k", type=int, default=4, help="--save avatar: body vertices (1..8) whose skin weights a mesh vertex blends")
     ap.add_argument("--avatar_bind_pose", type=int, default=0, help="--save avatar: the pose of the sequence at which the mesh is "
                     "extracted and bound; every pose becomes a key of the file's animation")
@@ -275,6 +281,11 @@ def main(argv=None):
         parser.error("--mesh_texture needs the frames it is baked from: pass --mesh_color_views K with K >= 1")
     if opt.mesh_texture and opt.save not in ("mesh", "avatar"):
         parser.error("--mesh_texture goes with --save mesh or --save avatar")
+    if not 0.0 <= opt.mesh_simplify < math.inf:
+        parser.error(f"--mesh_simplify {opt.mesh_simplify}: the cluster cell in voxels, 0 for off")
+    if opt.mesh_simplify and opt.save not in ("mesh", "avatar"):
+        parser.error("--mesh_simplify goes with --save mesh or --save avatar")
+    simplify = opt.mesh_simplify or None
     sweep_given = opt.n_angles is not None
     if opt.n_angles is None:
         opt.n_angles = 40
@@ -329,7 +340,7 @@ def main(argv=None):
             b = opt.avatar_bind_pose
             mesh, = generate_textured_meshes(generator, preprocessor, config, seed, {key: v[b:b + 1] for key, v in sequence.items()},
                                              opt.mesh_resolution, opt.mesh_level, opt.mesh_color_views, opt.mesh_color_range,
-                                             avatar_k=opt.avatar_k, texture_size=opt.mesh_texture)
+                                             avatar_k=opt.avatar_k, texture_size=opt.mesh_texture, simplify=simplify)
             look = dict(uvs=mesh["uvs"], texture=mesh["texture"]) if opt.mesh_texture else dict(colors=mesh["colors"])
             write_glb(os.path.join(out_dir, f"{seed:03d}_avatar.glb"), mesh["rest_vertices"], mesh["faces"], mesh["joints"],
                       mesh["weights"], skeleton["rest_joints"][b], skeleton["parents"], normals=mesh["rest_normals"],
@@ -344,11 +355,12 @@ def main(argv=None):
                 data = record if opt.smpl_record is not None else synthetic.make_conditions(1, 6890, seed=seed)
             if opt.mesh_normals or opt.mesh_color_views:
                 meshes = generate_textured_meshes(generator, preprocessor, config, seed, data, opt.mesh_resolution, opt.mesh_level,
-                                                  opt.mesh_color_views, opt.mesh_color_range, texture_size=opt.mesh_texture)
+                                                  opt.mesh_color_views, opt.mesh_color_range, texture_size=opt.mesh_texture,
+                                                  simplify=simplify)
                 textured = meshes
                 meshes = [(m["vertices"], m["faces"], m["normals"], m["colors"]) for m in meshes]
             else:
-                meshes = generate_meshes(generator, config, seed, data, opt.mesh_resolution, opt.mesh_level)
+                meshes = generate_meshes(generator, config, seed, data, opt.mesh_resolution, opt.mesh_level, simplify)
             for i, mesh in enumerate(meshes):
                 name = f"{seed:03d}_mesh_{i:03d}.ply" if opt.pose_sequence is not None else f"{seed:03d}_mesh.ply"
                 write_ply(os.path.join(out_dir, name), *mesh)

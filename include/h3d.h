@@ -1093,6 +1093,57 @@ int h3d_mesh_bind(const float* vertices, const float* normals, int64_t M, const 
 int h3d_mesh_pose(const float* rest_vertices, const float* rest_normals, const int32_t* joints, const float* weights, int64_t M,
                   const float* A, int n, int J, float* vertices, float* normals, h3d_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Simplification of a mesh by quadric vertex clustering (csrc/mesh_simplify.hip): the vertices are clustered on a uniform grid, each
+ * cluster is replaced by the point that minimises the summed plane quadrics of its triangles (Lindstrom's out-of-core scheme), and
+ * the triangles that collapse are dropped.  Three launches; between them the caller sorts (stable) the cell ids and the corner keys
+ * and takes the segment offsets.  No atomics, every sum in an order that the kernel alone fixes -- two runs give bit-identical
+ * tensors.  vertices [V,3] fp32, faces [T,3] int32, dense.
+ *   Grid: origin[3] HOST floats, cell > 0 and inv_cell = 1 / cell (fp32, divided on the host), counts (nx, ny, nz) >= 1 with
+ *   nx ny nz < 2^31; 3 T < 2^31 and V < 2^31 (cell ids, corner records and vertex ids are int32 quantities).
+ *   1. Cell of a vertex.  Per axis i = clamp(floorf((x - origin) * inv_cell), 0, n - 1): one fp32 subtraction and one fp32
+ *      multiplication, each rounded on its own, nothing fused; a coordinate that is not finite goes to index 0.
+ *      cell id = (ix ny + iy) nz + iz, int32.
+ *   2. Clusters are the non-empty cells; output vertex c belongs to the c-th non-empty cell in ascending cell id.  cluster [V] int32
+ *      = the output vertex that stands for each input vertex.
+ *   3. Quadric of a cluster, in coordinates local to the centre of its cell, centre_a = origin_a + (i_a + 1/2) cell (fp32, the
+ *      product rounded before the sum), p~ = p - centre, so that fp32 sums do not cancel.  Every face corner whose vertex lies in the
+ *      cluster is a corner record of the cluster (a face with two or three corners in one cluster has as many records there).  With
+ *      the face's three indices clamped into [0, V - 1] (as h3d_mesh_bake_texture clamps them), m = (p~1 - p~0) x (p~2 - p~0) and
+ *      w = 1 / (2 |m|), a record adds  A += w m m^T  and  b += w m (-m . p~0);  a record whose |m| is zero or not finite adds nothing.
+ *      mean = the mean of p~ over the cluster's vertices.
+ *   4. Representative.  t = trace A.  Where t > 0: x = mean - (A + lambda t I)^-1 (A mean + b), a symmetric positive definite 3 x 3
+ *      system of condition at most (1 + lambda) / lambda, solved by Cholesky in fp32; otherwise x = mean.  Where any axis of x is NaN,
+ *      x = 0 (the cell centre); then every axis is clamped to +-reach cell.  Output position = centre + x.  The pull towards the mean
+ *      is Tikhonov regularisation, continuous in every input: there is no rank threshold.  The clamp keeps every input vertex within
+ *      (reach + 1/2) cell per axis of the vertex that stands for it (a vertex outside the grid: of its clamped cell's box).
+ *   5. Faces.  Each face is remapped through `cluster`; it is kept iff its three clusters differ.  The caller keeps the flagged faces
+ *      in ascending face id, corner order (hence orientation) unchanged.  Equal faces are not merged, and a cluster that no kept face
+ *      names stays in the output.
+ *   h3d_mesh_cluster_cells  cells [V] int32 of step 1.
+ *   h3d_mesh_cluster_faces  one thread per face: out_faces [T,3] int32 = cluster[face] (indices clamped as above), keep [T] bytes
+ *                           (1: the three differ), keys [3T] int32: keys[3 t + k] = the cluster of corner k, the sort key of corner
+ *                           record 3 t + k.
+ *   h3d_mesh_cluster_solve  steps 3 and 4.  vertex_order [V] int64: the vertex ids sorted by (cluster, vertex id); record_order [3T]
+ *                           int64: the record ids 3 t + k sorted by (key, record id) -- both are what a stable sort returns;
+ *                           vertex_offsets, record_offsets [C + 1] int64: cluster c owns [offsets[c], offsets[c + 1]) of its list;
+ *                           cluster_cells [C] int32: the cell id of every cluster; out [C,3] fp32.
+ *                           One wavefront owns a cluster.  Summation order: lane l adds entries l, l + 64, l + 128, ... of the
+ *                           segment in this order, starting from zero; then the 64 lanes are combined by v += v(lane xor s) for
+ *                           s = 32, 16, 8, 4, 2, 1 -- the same for the six entries of A, the three of b, the three of the mean's
+ *                           sum and the vertex count.  Nothing of it depends on the launch geometry.  Every list entry, offset and
+ *                           face index is clamped into its tensor before it addresses memory: lists that do not belong to the mesh
+ *                           give wrong vertices, never an access out of range.
+ * V = 0, T = 0 and C = 0 are valid and launch nothing. */
+int h3d_mesh_cluster_cells(const float* vertices, int64_t V, const float* origin, float inv_cell, int nx, int ny, int nz,
+                           int32_t* cells, h3d_stream_t stream);
+int h3d_mesh_cluster_faces(const int32_t* faces, int64_t T, const int32_t* cluster, int64_t V, int32_t* out_faces, uint8_t* keep,
+                           int32_t* keys, h3d_stream_t stream);
+int h3d_mesh_cluster_solve(const float* vertices, int64_t V, const int32_t* faces, int64_t T, const int64_t* vertex_order,
+                           const int64_t* vertex_offsets, const int64_t* record_order, const int64_t* record_offsets,
+                           const int32_t* cluster_cells, int64_t C, const float* origin, float cell, int nx, int ny, int nz,
+                           float regularization, float reach, float* out, h3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
