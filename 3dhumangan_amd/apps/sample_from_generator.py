@@ -20,14 +20,14 @@ camera rotation, as `{seed:03d}_mesh.ply` -- one file per pose, `{seed:03d}_mesh
 `--mesh_normals` adds per-vertex normals (nx ny nz: the normalised gradient of the density) to those files, `--mesh_color_views K
 [--mesh_color_range DEG, default 30]` per-vertex colours as well (red green blue; it implies the normals): K frames panned evenly
 over +-DEG, each made as a frame of this app is made (RNGs seeded anew, the latent, the preprocessor, staged_forward -- the view at
-angle 0 is the frame the app saves for the seed and pose), carried onto the vertices by Map3DGenerator.project_views.  A vertex no
+angle 0 is the frame the app saves for the seed and pose), carried onto the vertices by geometry_export.colour.  A vertex no
 view sees stays at colour 0 (mid grey).  With random-init weights the frames are noise and so are the colours.  `--save avatar`
 (with `--pose-sequence`) writes ONE rigged mesh per seed, `{seed:03d}_avatar.glb` (binary glTF 2.0): the surface is extracted at pose
 `--avatar_bind_pose` of the sequence, takes the SMPL body's skin weights from its `--avatar_k` nearest body vertices and goes to the
 rest pose (Map3DGenerator.extract_avatar); the file holds the rest mesh with normals (colours with `--mesh_color_views`), the skin, the
 skeleton and every pose of the sequence as a key of one animation -- a viewer plays the motion without the network.
 `--mesh_texture S` (with `--mesh_color_views K`, K >= 1) bakes the same K frames into an S x S texture atlas
-(Map3DGenerator.bake_views): the avatar's `.glb` then carries the texture instead of vertex colours, and `--save mesh` writes, beside
+(the same stage): the avatar's `.glb` then carries the texture instead of vertex colours, and `--save mesh` writes, beside
 each `.ply` (unchanged), a static `.glb` of the same stem with the texture -- the appearance then has the resolution of the frames,
 whatever `--mesh_resolution` is.  `--mesh_simplify K` (with `--save mesh` / `--save avatar`) reduces every surface by quadric vertex
 clustering on cells of K voxels of the density grid (Map3DGenerator.extract_mesh(simplify=K)) before anything else is computed on it:
@@ -46,6 +46,7 @@ from .. import checkpoints, configs, synthetic
 from ..lib import data as lib_data
 from ..lib import generators as lib_generators
 from ..lib.components.mesh_io import write_glb, write_ply
+from ..lib.generators import geometry_export
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
@@ -187,26 +188,23 @@ def generate_textured_meshes(generator, preprocessor, config, seed, conditions, 
     and texture belong to the simplified mesh."""
     dev = generator.device
     pan = torch.linspace(-math.radians(view_range), math.radians(view_range), n_views) if n_views > 1 else torch.zeros(n_views)
+    method, rig = ("extract_textured_mesh", {}) if avatar_k is None else ("extract_avatar", {"k": avatar_k})
+    look = geometry_export.settings(method, config, n_views, level, texture_size=n_views and texture_size or None, simplify=simplify)
     meshes = []
     for i in range(conditions["vertices"].shape[0]):
         z = latent_for_seed(seed, config["latent_dim"]).to(dev)
         base = {k: v[i:i + 1].to(dev) for k, v in conditions.items()}
         base["scales"] = base["scales"].reshape(1)
         body = {k: base[k] for k in generator.MESH_CONDITIONS}
-        if avatar_k is None:
-            mesh, = generator.extract_textured_mesh(z, body, [], level=level, resolution=resolution, simplify=simplify, **config)
-        else:
-            mesh, = generator.extract_avatar(z, body, k=avatar_k, level=level, resolution=resolution, simplify=simplify, **config)
-        views, frames = [], []
+        mesh, = getattr(generator, method)(z, body, views=[], level=level, resolution=resolution, simplify=simplify, **rig, **config)
+        views, frames = [], []                              # the app's own, after the geometry: the RNGs are seeded anew per view
         for a_h in pan.to(dev):
             z = latent_for_seed(seed, config["latent_dim"]).to(dev)
             a_h = a_h.reshape(1, 1)
             views.append(preprocessor.forward_with_rotation(dict(base), a_h, torch.zeros_like(a_h), torch.zeros_like(a_h), **config))
-            frames.append(generator.mesh_view(z, views[-1], **config))
+            frames.append(geometry_export.view_frame(generator, z, views[-1], config))
         if views:
-            mesh["colors"], mesh["coverage"] = generator.project_views(mesh, views, frames, 0, generator.default_depth_tolerance(config))
-            if texture_size:
-                mesh.update(generator.bake_views(mesh, views, frames, 0, generator.default_depth_tolerance(config), texture_size))
+            geometry_export.colour([mesh], views, frames, look.depth_tolerance, look.normal_power, look.texture_size)
         meshes.append(mesh)
     return meshes
 
@@ -357,15 +355,13 @@ def main(argv=None):
                 meshes = generate_textured_meshes(generator, preprocessor, config, seed, data, opt.mesh_resolution, opt.mesh_level,
                                                   opt.mesh_color_views, opt.mesh_color_range, texture_size=opt.mesh_texture,
                                                   simplify=simplify)
-                textured = meshes
-                meshes = [(m["vertices"], m["faces"], m["normals"], m["colors"]) for m in meshes]
             else:
-                meshes = generate_meshes(generator, config, seed, data, opt.mesh_resolution, opt.mesh_level, simplify)
-            for i, mesh in enumerate(meshes):
+                meshes = [dict(vertices=v, faces=f) for v, f in generate_meshes(generator, config, seed, data, opt.mesh_resolution,
+                                                                                opt.mesh_level, simplify)]
+            for i, m in enumerate(meshes):
                 name = f"{seed:03d}_mesh_{i:03d}.ply" if opt.pose_sequence is not None else f"{seed:03d}_mesh.ply"
-                write_ply(os.path.join(out_dir, name), *mesh)
+                write_ply(os.path.join(out_dir, name), m["vertices"], m["faces"], m.get("normals"), m.get("colors"))
                 if opt.mesh_texture:
-                    m = textured[i]
                     write_glb(os.path.join(out_dir, name[:-4] + ".glb"), m["vertices"], m["faces"], normals=m["normals"], uvs=m["uvs"],
                               texture=m["texture"])
             continue

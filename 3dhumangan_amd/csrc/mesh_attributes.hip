@@ -253,6 +253,17 @@ bool positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }
 
 }  // namespace
 
+// what h3d_mesh_project_colors and h3d_mesh_bake_texture both ask of the views
+static int check_views(const char* who, int K, int H, int W, int h, int w, float depth_tolerance, float eps, int normal_power) {
+    H3D_REQUIRE(K >= 1, "%s: K=%d views (at least 1)", who, K);
+    H3D_REQUIRE(H >= 2 && W >= 2 && h >= 2 && w >= 2, "%s: images %dx%d and depths %dx%d need at least 2x2", who, H, W, h, w);
+    H3D_REQUIRE((int64_t)K * 3 * H * W < ((int64_t)1 << 40) && (int64_t)K * h * w < ((int64_t)1 << 40), "%s: views too large", who);
+    H3D_REQUIRE(positive_finite(depth_tolerance), "%s: depth_tolerance=%g must be positive", who, depth_tolerance);
+    H3D_REQUIRE(positive_finite(eps), "%s: eps=%g must be positive", who, eps);
+    H3D_REQUIRE(normal_power >= 1 && normal_power <= 8, "%s: normal_power=%d outside 1..8", who, normal_power);
+    return H3D_OK;
+}
+
 extern "C" int h3d_isosurface_normals(const float* volume, int Nx, int Ny, int Nz, const float* origin, const float* spacing,
                                       const float* vertices, int64_t V, float* normals, float* gradient, h3d_stream_t stream) {
     H3D_REQUIRE(volume && origin && spacing, "h3d_isosurface_normals: null pointer");
@@ -276,14 +287,7 @@ extern "C" int h3d_mesh_project_colors(const float* vertices, const float* norma
                                        int W, const float* depths, int h, int w, const float* table, float depth_tolerance,
                                        int normal_power, float fill, float eps, float* colors, float* coverage,
                                        h3d_stream_t stream) {
-    H3D_REQUIRE(K >= 1, "h3d_mesh_project_colors: K=%d views (at least 1)", K);
-    H3D_REQUIRE(H >= 2 && W >= 2 && h >= 2 && w >= 2, "h3d_mesh_project_colors: images %dx%d and depths %dx%d need at least 2x2", H,
-                W, h, w);
-    H3D_REQUIRE((int64_t)K * 3 * H * W < ((int64_t)1 << 40) && (int64_t)K * h * w < ((int64_t)1 << 40),
-                "h3d_mesh_project_colors: views too large");
-    H3D_REQUIRE(positive_finite(depth_tolerance), "h3d_mesh_project_colors: depth_tolerance=%g must be positive", depth_tolerance);
-    H3D_REQUIRE(positive_finite(eps), "h3d_mesh_project_colors: eps=%g must be positive", eps);
-    H3D_REQUIRE(normal_power >= 1 && normal_power <= 8, "h3d_mesh_project_colors: normal_power=%d outside 1..8", normal_power);
+    if (int rc = check_views("h3d_mesh_project_colors", K, H, W, h, w, depth_tolerance, eps, normal_power)) return rc;
     H3D_REQUIRE(V >= 0 && V < ((int64_t)1 << 31) * kThreads, "h3d_mesh_project_colors: V=%lld out of range", (long long)V);
     if (V == 0) return H3D_OK;
     H3D_REQUIRE(vertices && normals && images && depths && table && colors && coverage, "h3d_mesh_project_colors: null pointer");
@@ -311,14 +315,7 @@ extern "C" int h3d_mesh_bake_texture(const float* vertices, const float* normals
     const int c = S / R;
     H3D_REQUIRE(c >= 4, "h3d_mesh_bake_texture: T=%lld triangles need a texture of at least %d texels a side (cells of 4), got S=%d",
                 (long long)T, 4 * R, S);
-    H3D_REQUIRE(K >= 1, "h3d_mesh_bake_texture: K=%d views (at least 1)", K);
-    H3D_REQUIRE(H >= 2 && W >= 2 && h >= 2 && w >= 2, "h3d_mesh_bake_texture: images %dx%d and depths %dx%d need at least 2x2", H, W,
-                h, w);
-    H3D_REQUIRE((int64_t)K * 3 * H * W < ((int64_t)1 << 40) && (int64_t)K * h * w < ((int64_t)1 << 40),
-                "h3d_mesh_bake_texture: views too large");
-    H3D_REQUIRE(positive_finite(depth_tolerance), "h3d_mesh_bake_texture: depth_tolerance=%g must be positive", depth_tolerance);
-    H3D_REQUIRE(positive_finite(eps), "h3d_mesh_bake_texture: eps=%g must be positive", eps);
-    H3D_REQUIRE(normal_power >= 1 && normal_power <= 8, "h3d_mesh_bake_texture: normal_power=%d outside 1..8", normal_power);
+    if (int rc = check_views("h3d_mesh_bake_texture", K, H, W, h, w, depth_tolerance, eps, normal_power)) return rc;
     H3D_REQUIRE(V >= 0 && V < ((int64_t)1 << 31), "h3d_mesh_bake_texture: V=%lld out of range", (long long)V);
     H3D_REQUIRE(T == 0 || V >= 1, "h3d_mesh_bake_texture: %lld triangles without a vertex", (long long)T);
     H3D_REQUIRE(texture && coverage, "h3d_mesh_bake_texture: null pointer");

@@ -25,12 +25,9 @@ import torch.nn as nn
 
 from ... import _lib
 from ..._stages import stage
-from ..components import mesh_rig, smpl
-from ..components.isosurface import marching_tetrahedra, vertex_normals
-from ..components.mesh_color import project_colors
-from ..components.mesh_simplify import simplify as simplify_mesh
-from ..components.mesh_texture import atlas_uvs, bake_texture
+from ..components import smpl
 from ..components.ops.bias_act import bias_act
+from . import geometry_export
 from . import volume_rendering as vr
 from .differentiable import synthesis_forward
 from .modsynth_pack import ModSynthesisPlan
@@ -809,34 +806,10 @@ class Map3DGenerator(nn.Module):
         simplify=K (a positive number, None: off): the surface is reduced by quadric vertex clustering (lib/components/
         mesh_simplify.py) on cells of K voxels of the density grid, laid over the grid's own box: 12 / 27 / 49 times fewer triangles
         at K = 2 / 3 / 4 on a sphere, with the shape the fine grid saw."""
-        clamp = config.get("clamp_mode", "relu")
-        if clamp != "relu":
-            raise NotImplementedError(f"extract_mesh: clamp_mode={clamp!r} is not supported: only with 'relu' is the raw output of "
-                                      "the density head the density the renderer integrates (above zero)")
-        if level is None:
-            level = math.log(2.0) * config.get("num_steps", 24) / (config["ray_end"] - config["ray_start"])
-        simplify = self._check_simplify("extract_mesh", simplify)
+        s = geometry_export.settings("extract_mesh", config, level=level, simplify=simplify)
         sigma, origin, spacing = self.density_grid(latent, conditions, **config)
         with torch.cuda.device(sigma.device):
-            return [self._simplified(marching_tetrahedra(sigma[b], level, o, s), simplify, sigma.shape[1:], o, s)
-                    for b, (o, s) in enumerate(zip(origin.tolist(), spacing.tolist()))]
-
-    @staticmethod
-    def _check_simplify(who, simplify):
-        if simplify is None:
-            return None
-        if isinstance(simplify, bool) or not isinstance(simplify, (int, float)) or not 0.0 < float(simplify) < math.inf:
-            raise ValueError(f"{who}: simplify={simplify!r} must be a positive number (the cluster cell in voxels) or None")
-        return float(simplify)
-
-    @staticmethod
-    def _simplified(mesh, simplify, nodes, origin, spacing):
-        """(vertices, faces) clustered on cells of `simplify` voxels over the box of the density grid (`nodes` per axis from `origin`
-        at `spacing`, cubic voxels): counts floor((N - 1) / simplify) + 1 per axis; simplify=None: `mesh` itself"""
-        if simplify is None:
-            return mesh
-        counts = [int(math.floor((n - 1) / simplify)) + 1 for n in nodes]
-        return simplify_mesh(mesh[0], mesh[1], simplify * spacing[0], origin=origin, counts=counts)[:2]
+            return [(m["vertices"], m["faces"]) for m in geometry_export.surfaces(sigma, origin, spacing, s.level, s.simplify, False)]
 
     @torch.no_grad()
     def extract_textured_mesh(self, latent, conditions, views, level=None, depth_tolerance=None, normal_power=2, texture_size=None,
@@ -859,37 +832,19 @@ class Map3DGenerator(nn.Module):
         colors / coverage are what they are without it.
         simplify=K: as in extract_mesh; the normals, colours and texture are evaluated at the simplified mesh's own vertices and
         faces (nothing is carried across), so every triangle's cell of the atlas grows with the reduction."""
-        clamp = config.get("clamp_mode", "relu")
-        if clamp != "relu":
-            raise NotImplementedError(f"extract_textured_mesh: clamp_mode={clamp!r} is not supported: only with 'relu' is the raw output "
-                                      "of the density head the density the renderer integrates (above zero)")
-        if int(normal_power) != normal_power or not 1 <= int(normal_power) <= 8:
-            raise ValueError(f"extract_textured_mesh: normal_power={normal_power} must be an integer 1..8")
         views = list(views)
-        if texture_size is not None and not views:
-            raise ValueError("extract_textured_mesh: texture_size needs at least one view to bake the texture from")
-        if level is None:
-            level = math.log(2.0) * config.get("num_steps", 24) / (config["ray_end"] - config["ray_start"])
-        if depth_tolerance is None:
-            depth_tolerance = self.default_depth_tolerance(config)
-        if not 0.0 < float(depth_tolerance) < float("inf"):
-            raise ValueError(f"extract_textured_mesh: depth_tolerance={depth_tolerance} must be positive")
-        simplify = self._check_simplify("extract_textured_mesh", simplify)
+        s = geometry_export.settings("extract_textured_mesh", config, len(views), level, depth_tolerance, normal_power, texture_size, simplify)
+        return self._textured_meshes(latent, conditions, views, s, config)
+
+    def _textured_meshes(self, latent, conditions, views, s, config):
+        """behind the settings `s`: the geometry of every item, then the frames in the order of `views`, then the colours"""
         sigma, origin, spacing = self.density_grid(latent, conditions, **config)
         with torch.cuda.device(sigma.device):
-            meshes = []
-            for b, (o, s) in enumerate(zip(origin.tolist(), spacing.tolist())):
-                vertices, faces = self._simplified(marching_tetrahedra(sigma[b], level, o, s), simplify, sigma.shape[1:], o, s)
-                meshes.append(dict(vertices=vertices, faces=faces, normals=vertex_normals(sigma[b], vertices, o, s), colors=None,
-                                   coverage=None))
+            meshes = geometry_export.surfaces(sigma, origin, spacing, s.level, s.simplify, True)
             if not views:
                 return meshes
-            frames = [self.mesh_view(latent, view, **config) for view in views]
-            for b, mesh in enumerate(meshes):
-                mesh["colors"], mesh["coverage"] = self.project_views(mesh, views, frames, b, depth_tolerance, normal_power)
-                if texture_size is not None:
-                    mesh.update(self.bake_views(mesh, views, frames, b, depth_tolerance, texture_size, normal_power))
-            return meshes
+            frames = [geometry_export.view_frame(self, latent, view, config) for view in views]
+            return geometry_export.colour(meshes, views, frames, s.depth_tolerance, s.normal_power, s.texture_size)
 
     @torch.no_grad()
     def extract_avatar(self, latent, conditions, k=4, level=None, views=(), texture_size=None, simplify=None, **config):
@@ -903,51 +858,10 @@ class Map3DGenerator(nn.Module):
         other pose of the skeleton; with this item's fk_matrices it gives back `vertices`.  `views`, `level` and the config: as in
         extract_textured_mesh (views=() gives no colours).  texture_size: as there; the UVs belong to the faces, so the texture baked
         in the posed space serves the rest mesh unchanged.  simplify=K: as there; the simplified vertices are the ones bound."""
-        clamp = config.get("clamp_mode", "relu")
-        if clamp != "relu":
-            raise NotImplementedError(f"extract_avatar: clamp_mode={clamp!r} is not supported: only with 'relu' is the raw output of "
-                                      "the density head the density the renderer integrates (above zero)")
-        meshes = self.extract_textured_mesh(latent, conditions, views, level=level, texture_size=texture_size, simplify=simplify,
-                                            **config)
+        views = list(views)
+        s = geometry_export.settings("extract_avatar", config, len(views), level, texture_size=texture_size, simplify=simplify)
+        meshes = self._textured_meshes(latent, conditions, views, s, config)
         with torch.cuda.device(latent.device):
-            for b, mesh in enumerate(meshes):
-                lbs = conditions["lbs_weights"]
-                mesh.update(mesh_rig.bind(mesh["vertices"], conditions["vertices"][b], lbs[b] if lbs.dim() == 3 else lbs,
-                                          conditions["fk_matrices"][b], normals=mesh["normals"], k=k))
-        return meshes
+            return geometry_export.rig(meshes, conditions, k)
 
-    @staticmethod
-    def default_depth_tolerance(config):
-        """two coarse integration steps of the render, in world units"""
-        return 2.0 * (config["ray_end"] - config["ray_start"]) / config.get("num_steps", 24)
-
-    @torch.no_grad()
-    def mesh_view(self, latent, view, **config):
-        """One view for extract_textured_mesh: staged_forward(latent, view, keep_depth_on_device=True, **config) ->
-        (rgbs fp32 [B,3,H,W] clamped to [-1, 1] as the apps clamp a frame, the distance along each ray fp32 [B,h,w] in world units:
-        staged_forward's normalised depth map taken back, depth_map * depth_length / 2 + focal / scale; it saturates where the map
-        was clamped)."""
-        out = self.staged_forward(latent, view, **dict(config, keep_depth_on_device=True))
-        zc = view["intrinsics"][:, 0, 0] / view["scales"].float()
-        return out["rgbs"].float().clamp(-1, 1), out["depths"][:, 0].float() * (config["depth_length"] / 2.0) + zc.view(-1, 1, 1)
-
-    @staticmethod
-    def _view_tensors(views, frames, b):
-        """item `b` of every view (conditions dicts) and its mesh_view frame, stacked -> (images, depths, focals, scales, cam2world)"""
-        return (torch.stack([im[b] for im, _ in frames]), torch.stack([d[b] for _, d in frames]),
-                torch.stack([v["intrinsics"][b, 0, 0] for v in views]).float(), torch.stack([v["scales"][b] for v in views]).float(),
-                torch.stack([v["cam2world_matrices"][b] for v in views]).float())
-
-    @staticmethod
-    def project_views(mesh, views, frames, b, depth_tolerance, normal_power=2):
-        """project_colors of item `b` of every view (conditions dicts) and its mesh_view frame onto `mesh` -> (colors, coverage)"""
-        return project_colors(mesh["vertices"], mesh["normals"], *Map3DGenerator._view_tensors(views, frames, b), depth_tolerance,
-                              normal_power)
-
-    @staticmethod
-    def bake_views(mesh, views, frames, b, depth_tolerance, texture_size, normal_power=2):
-        """bake_texture of the same views and frames as project_views -> dict(uvs [T,3,2], texture [S,S,3], texture_coverage [S,S])"""
-        texture, coverage = bake_texture(mesh["vertices"], mesh["faces"], mesh["normals"], *Map3DGenerator._view_tensors(views, frames, b),
-                                         depth_tolerance, texture_size, normal_power)
-        uvs = torch.from_numpy(atlas_uvs(mesh["faces"].shape[0], texture_size)).to(texture.device)
-        return {"uvs": uvs, "texture": texture, "texture_coverage": coverage}
+    default_depth_tolerance = staticmethod(geometry_export.default_depth_tolerance)

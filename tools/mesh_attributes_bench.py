@@ -35,6 +35,7 @@ L = importlib.import_module("3dhumangan_amd._lib")
 iso = importlib.import_module("3dhumangan_amd.lib.components.isosurface")
 mesh_color = importlib.import_module("3dhumangan_amd.lib.components.mesh_color")
 synthetic = importlib.import_module("3dhumangan_amd.synthetic")
+geometry_export = importlib.import_module("3dhumangan_amd.lib.generators.geometry_export")
 
 GRID = (179, 256, 178)
 
@@ -143,7 +144,7 @@ def whole(reps, K, resolution, dev):
     plain = lambda: G.extract_mesh(z, body, level=level, **cfg)
     with_normals = lambda: G.extract_textured_mesh(z, body, [], level=level, **cfg)
     textured = lambda: G.extract_textured_mesh(z, body, views, level=level, **cfg)
-    frames = lambda: [G.mesh_view(z, view, **cfg) for view in views]
+    frames = lambda: [geometry_export.view_frame(G, z, view, cfg) for view in views]
     out = {"config": "MAP3DBN512 at 512x256 over 96x48 rays, 32 steps, random-init weights, procedural body", "views": K,
            "grid": list(sigma.shape[1:]), "level": level}
     n = max(3, reps // 2)
