@@ -24,8 +24,8 @@ constexpr int kThreads = 256;
 constexpr int kKS = 16;                       // rows per k-step
 
 struct Args {
-    const void* dY;               // fp32, or f16 when `half` (AMP: activations and their gradients travel as f16; an f16 value's bf16
-    const void* X;                // hi / lo split is exact, so the arithmetic below is unchanged and exact in the operands)
+    const void* dY;               // fp32, or f16 when `half` (AMP: activations and their gradients travel as f16; the HALF instantiations
+    const void* X;                // multiply the f16 values themselves -- one F16 matrix product, Frag<true>::mul -- no bf16 split)
     float* partial;
     int64_t M;
     int Co, Ci, ldy, ldx, rows_per_wg;
