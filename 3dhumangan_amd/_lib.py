@@ -93,6 +93,7 @@ _SIGNATURES = {
     "h3d_synthesis_x3_tiles": (C.c_int, [_p, _l, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p]),
     "h3d_synthesis_check": (C.c_int, [_p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "h3d_synthesis_x3t_tiles": (C.c_int, [_i]),
+    "h3d_synthesis_x3t_structure": (C.c_int, [_p]),
     "h3d_synthesis_x3t": (C.c_int, [_p, _p, _p, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _p]),
     "h3d_synthesis_x3t_tier": (C.c_int, [_p, _p, _p, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p]),
     "h3d_synthesis_x3t_tier_guarded": (C.c_int, [_p, _p, _p, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
@@ -103,6 +104,7 @@ _SIGNATURES = {
     "h3d_style_input_lds_bytes": (C.c_int64, [_i, _i]),
     "h3d_style_input": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "h3d_synthesis_x3_geometry_ok": (C.c_int, [_i, _i, _i, _i]),
+    "h3d_synthesis_x3_structure": (C.c_int, [_p, _i]),
     "h3d_synthesis_x3_lds_bytes": (C.c_int64, [_i, _i, _i, _i, _i]),
     "h3d_sample_pdf": (C.c_int, [_p, _p, _p, _p, _l, _i, _i, _f, _p]),
     "h3d_ray_points": (C.c_int, [_p, _p, _p, _p, _i, _l, _i, _p]),

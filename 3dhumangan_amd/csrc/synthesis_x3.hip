@@ -719,6 +719,50 @@ extern "C" int h3d_synthesis_x3_geometry_ok(int H, int W, int Hr, int Wr) {
     return H >= 1 && Hr >= 1 && Wr >= 1 && W >= 32 && W % 32 == 0 && (int64_t)31 * Wr < (int64_t)6 * W;
 }
 
+// The structural rules of the register engines: what the layout of a descriptor (width, skip and style flags) must look like,
+// whatever its tables hold.  -> H3D_OK with the first skip block (n_blocks: none) and the length of the leading run of per-pixel-style
+// blocks, or H3D_EUNSUPPORTED.  n_blocks is the caller's to check.
+static int x3_structure(const h3d_synth_desc* desc, int& first_skip, int& n_pixel_blocks) {
+    if (desc->C > 256) {
+        h3d::set_error("h3d_synthesis_x3: width %d exceeds the 256 this engine keeps in registers (use h3d_synthesis)", desc->C);
+        return H3D_EUNSUPPORTED;
+    }
+    first_skip = desc->n_blocks;
+    for (int k = 0; k < desc->n_blocks; ++k) {
+        const h3d_block_desc& b = desc->block[k];
+        if (first_skip < k && !b.skip) {
+            h3d::set_error("h3d_synthesis_x3: a block without skip connection after the first skip block is not supported; "
+                           "use h3d_synthesis");
+            return H3D_EUNSUPPORTED;
+        }
+        if (b.skip && first_skip == desc->n_blocks) first_skip = k;
+        if (first_skip <= k && (b.spade[0].pixel_style || b.spade[1].pixel_style)) {
+            h3d::set_error("h3d_synthesis_x3: a per-pixel-style block after the first skip block needs a third "
+                           "accumulator set; use h3d_synthesis");
+            return H3D_EUNSUPPORTED;
+        }
+    }
+    // per-pixel styles must form a leading run of whole blocks (both SPADEs), everything after it constant style
+    n_pixel_blocks = 0;
+    while (n_pixel_blocks < desc->n_blocks && desc->block[n_pixel_blocks].spade[0].pixel_style &&
+           desc->block[n_pixel_blocks].spade[1].pixel_style)
+        ++n_pixel_blocks;
+    for (int k = n_pixel_blocks; k < desc->n_blocks; ++k)
+        if (desc->block[k].spade[0].pixel_style || desc->block[k].spade[1].pixel_style) {
+            h3d::set_error("h3d_synthesis_x3: per-pixel-style SPADEs must be the leading whole blocks (block %d breaks that); "
+                           "use h3d_synthesis_x3t / h3d_synthesis", k);
+            return H3D_EUNSUPPORTED;
+        }
+    return H3D_OK;
+}
+
+extern "C" int h3d_synthesis_x3_structure(const h3d_synth_desc* desc, int /* x2: the two engines share every rule */) {
+    H3D_REQUIRE(desc, "h3d_synthesis_x3_structure: null pointer");
+    H3D_REQUIRE(desc->n_blocks >= 1 && desc->n_blocks <= H3D_MAX_BLOCKS, "h3d_synthesis_x3_structure: n_blocks=%d", desc->n_blocks);
+    int first_skip, n_pixel_blocks;
+    return x3_structure(desc, first_skip, n_pixel_blocks);
+}
+
 static int synthesis_x(bool x2, const void* stream, int64_t total_stages, const float* tables, int table_floats,
                        const h3d_synth_desc* desc, const float* G, int g_channels, int Hr, int Wr,
                        const float* cst, int n_cst, const float* ab, int n_ab, float* rgb, int B, int H, int W,
@@ -727,31 +771,16 @@ static int synthesis_x(bool x2, const void* stream, int64_t total_stages, const 
     H3D_REQUIRE(h3d::aligned16(stream) && h3d::aligned16(tables), "h3d_synthesis_x3: stream/tables must be 16-byte aligned");
     H3D_REQUIRE(desc->n_blocks >= 1 && desc->n_blocks <= H3D_MAX_BLOCKS, "h3d_synthesis_x3: n_blocks=%d", desc->n_blocks);
     H3D_REQUIRE(B >= 0 && B <= 65535 && H >= 1 && W >= 1, "h3d_synthesis_x3: bad output shape");
-    if (desc->C > 256) {
-        h3d::set_error("h3d_synthesis_x3: width %d exceeds the 256 this engine keeps in registers (use h3d_synthesis)", desc->C);
-        return H3D_EUNSUPPORTED;
-    }
+    int first_skip, n_pixel_blocks;
+    if (const int rc = x3_structure(desc, first_skip, n_pixel_blocks)) return rc;
     const int NT = desc->C > 128 ? 8 : 4;
     int64_t want = 0;
-    bool seen_skip = false, any_pixel = false, any_const = false;
-    int first_skip = desc->n_blocks;
-    for (int k = 0; k < desc->n_blocks; ++k) {
-        if (desc->block[k].skip && !seen_skip) first_skip = k;
-        if (seen_skip && !desc->block[k].skip) {
-            h3d::set_error("h3d_synthesis_x3: a block without skip connection after the first skip block is not supported; "
-                           "use h3d_synthesis");
-            return H3D_EUNSUPPORTED;
-        }
-        seen_skip = seen_skip || desc->block[k].skip;
+    bool any_pixel = false, any_const = false;
+    for (int k = 0; k < desc->n_blocks; ++k)
         for (int s = 0; s < 2; ++s) {
             const h3d_spade_desc& sp = desc->block[k].spade[s];
             if (sp.pixel_style) {
                 any_pixel = true;
-                if (seen_skip) {
-                    h3d::set_error("h3d_synthesis_x3: a per-pixel-style block after the first skip block needs a third "
-                                   "accumulator set; use h3d_synthesis");
-                    return H3D_EUNSUPPORTED;
-                }
                 H3D_REQUIRE(sp.g_offset >= 0 && sp.g_offset + kShared <= g_channels && (sp.g_offset & 3) == 0,
                             "h3d_synthesis_x3: g_offset out of range");
                 H3D_REQUIRE(sp.cst_index >= 0 && sp.cst_index < n_cst, "h3d_synthesis_x3: cst_index out of range");
@@ -761,18 +790,6 @@ static int synthesis_x(bool x2, const void* stream, int64_t total_stages, const 
                 H3D_REQUIRE(sp.ab_index >= 0 && sp.ab_index < n_ab, "h3d_synthesis_x3: ab_index out of range");
             }
             want += 2 * NT;
-        }
-    }
-    // per-pixel styles must form a leading run of whole blocks (both SPADEs), everything after it constant style
-    int n_pixel_blocks = 0;
-    while (n_pixel_blocks < desc->n_blocks && desc->block[n_pixel_blocks].spade[0].pixel_style &&
-           desc->block[n_pixel_blocks].spade[1].pixel_style)
-        ++n_pixel_blocks;
-    for (int k = n_pixel_blocks; k < desc->n_blocks; ++k)
-        if (desc->block[k].spade[0].pixel_style || desc->block[k].spade[1].pixel_style) {
-            h3d::set_error("h3d_synthesis_x3: per-pixel-style SPADEs must be the leading whole blocks (block %d breaks that); "
-                           "use h3d_synthesis_x3t / h3d_synthesis", k);
-            return H3D_EUNSUPPORTED;
         }
     // x2 plans (round 6): a constant-style SPADE in front of the first skip block with g_offset == 1 has its convolution's stages in
     // the x3 format (bf16 hi | lo) and runs on three products; all of those blocks or none

@@ -478,6 +478,39 @@ extern "C" int h3d_synthesis_x3t_tiles(int C) {
     return nt + (nt & 1);
 }
 
+// The structural rules of the LDS-resident engine: what the layout of a descriptor (width, skip and style flags) must look like,
+// whatever its tables hold.  -> H3D_OK with the first skip block (n_blocks: none), or H3D_EUNSUPPORTED.  n_blocks is the caller's
+// to check.
+static int x3t_structure(const h3d_synth_desc* desc, int& first_skip) {
+    if (h3d_synthesis_x3t_tiles(desc->C) < 0) {
+        h3d::set_error("h3d_synthesis_x3t: width %d exceeds the 448 its LDS tile holds (use h3d_synthesis)", desc->C);
+        return H3D_EUNSUPPORTED;
+    }
+    first_skip = desc->n_blocks;
+    for (int k = 0; k < desc->n_blocks; ++k) {
+        if (desc->block[k].skip && first_skip == desc->n_blocks) first_skip = k;
+        if (k > first_skip && !desc->block[k].skip) {
+            h3d::set_error("h3d_synthesis_x3t: a block without skip connection after the first skip block is not supported; "
+                           "use h3d_synthesis");
+            return H3D_EUNSUPPORTED;
+        }
+    }
+    for (int k = 0; k < desc->n_blocks; ++k)
+        if (desc->block[k].skip && (desc->block[k].spade[0].pixel_style || desc->block[k].spade[1].pixel_style)) {
+            h3d::set_error("h3d_synthesis_x3t: a per-pixel-style SPADE inside a skip block needs a third accumulator "
+                           "set; use h3d_synthesis");
+            return H3D_EUNSUPPORTED;
+        }
+    return H3D_OK;
+}
+
+extern "C" int h3d_synthesis_x3t_structure(const h3d_synth_desc* desc) {
+    H3D_REQUIRE(desc, "h3d_synthesis_x3t_structure: null pointer");
+    H3D_REQUIRE(desc->n_blocks >= 1 && desc->n_blocks <= H3D_MAX_BLOCKS, "h3d_synthesis_x3t_structure: n_blocks=%d", desc->n_blocks);
+    int first_skip;
+    return x3t_structure(desc, first_skip);
+}
+
 static int synthesis_x3t_tier(const void* wblob, const float* tables, const h3d_synth_desc* desc, const float* G,
                               int g_channels, int Hr, int Wr, const float* cst, int n_cst, const float* ab, int n_ab,
                               float* rgb, int B, int H, int W, int dtype, int products, h3d_stream_t stream, int* ovf,
@@ -489,32 +522,16 @@ static int synthesis_x3t_tier(const void* wblob, const float* tables, const h3d_
     H3D_REQUIRE(h3d::aligned16(wblob) && h3d::aligned16(tables), "h3d_synthesis_x3t: weights / tables must be 16-byte aligned");
     H3D_REQUIRE(desc->n_blocks >= 1 && desc->n_blocks <= H3D_MAX_BLOCKS, "h3d_synthesis_x3t: n_blocks=%d", desc->n_blocks);
     H3D_REQUIRE(B >= 0 && B <= 65535 && H >= 1 && W >= 1, "h3d_synthesis_x3t: bad output shape");
+    int first_skip;
+    if (const int rc = x3t_structure(desc, first_skip)) return rc;
     const int NT = h3d_synthesis_x3t_tiles(desc->C);
-    if (NT < 0) {
-        h3d::set_error("h3d_synthesis_x3t: width %d exceeds the 448 its LDS tile holds (use h3d_synthesis)", desc->C);
-        return H3D_EUNSUPPORTED;
-    }
     bool any_pixel = false, any_const = false;
-    int first_skip = desc->n_blocks;
-    for (int k = 0; k < desc->n_blocks; ++k) {
-        if (desc->block[k].skip && first_skip == desc->n_blocks) first_skip = k;
-        if (k > first_skip && !desc->block[k].skip) {
-            h3d::set_error("h3d_synthesis_x3t: a block without skip connection after the first skip block is not supported; "
-                           "use h3d_synthesis");
-            return H3D_EUNSUPPORTED;
-        }
-    }
     for (int k = 0; k < desc->n_blocks; ++k)
         for (int s = 0; s < 2; ++s) {
             const h3d_spade_desc& sp = desc->block[k].spade[s];
             H3D_REQUIRE((sp.w_conv & 15) == 0 && (sp.b_conv & 3) == 0, "h3d_synthesis_x3t: misaligned conv offsets");
             if (sp.pixel_style) {
                 any_pixel = true;
-                if (desc->block[k].skip) {
-                    h3d::set_error("h3d_synthesis_x3t: a per-pixel-style SPADE inside a skip block needs a third accumulator "
-                                   "set; use h3d_synthesis");
-                    return H3D_EUNSUPPORTED;
-                }
                 H3D_REQUIRE(sp.g_offset >= 0 && sp.g_offset + kShared <= g_channels && (sp.g_offset & 3) == 0,
                             "h3d_synthesis_x3t: block %d spade %d g_offset out of range", k, s);
                 H3D_REQUIRE(sp.cst_index >= 0 && sp.cst_index < n_cst, "h3d_synthesis_x3t: cst_index out of range");

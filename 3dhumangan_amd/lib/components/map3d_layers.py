@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 
 from ... import _lib
-from ..generators.synthesis_pack import pack_matrix
+from ..generators.fragment_pack import pack_matrix
 from .ops.linear import linear as native_linear
 
 

@@ -31,12 +31,8 @@ from . import geometry_export
 from . import volume_rendering as vr
 from .differentiable import synthesis_forward
 from .modsynth_pack import ModSynthesisPlan
-from .style_input_pack import StyleInputPlan
+from .style_input_pack import StyleInputPlan, normalize_2nd_moment
 from .synthesis_pack import SynthesisPlan
-
-
-def normalize_2nd_moment(x, dim=1, eps=1e-8):
-    return x * (x.square().mean(dim=dim, keepdim=True) + eps).rsqrt()
 
 
 def _consume_camera_rng(sample_dist, batch, device):

@@ -26,7 +26,7 @@ import torch
 
 from ... import _lib
 from ..._stages import stage
-from .synthesis_pack import _pad, pack_matrix
+from .fragment_pack import _pad, pack_matrix
 
 EPS = 1e-8          # SpatialStyleModLayer's eps (map3d_layers.py:29)
 

@@ -19,7 +19,7 @@ import torch
 
 from ... import _lib
 from ..._stages import stage
-from .synthesis_pack import _pad, pack_matrix
+from .fragment_pack import _pad, pack_matrix
 
 
 def normalize_2nd_moment(x, dim=1, eps=1e-8):

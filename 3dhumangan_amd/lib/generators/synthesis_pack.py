@@ -3,10 +3,10 @@
 Everything here is *exact* algebra on the reference's eval-mode forward
 (lib/generators/map3d_generator.py:58-97, lib/components/map3d_layers.py:176-238):
 
-  static, once per weight version (build_plan):
+  static, once per weight version (SynthesisPlan: one parse of the state dict, one lazily built plan per engine family):
     conv weight  = weight_orig / (u . (W v))                (nn.utils.spectral_norm in eval, stored u/v)
     BatchNorm    = x * sc + sh,  sc = weight * rsqrt(running_var + eps),  sh = bias - running_mean * sc
-    all matrices packed into MFMA B-fragment order (include/h3d.h)
+    all matrices packed into the engine's MFMA fragment format (fragment_pack.py, include/h3d.h)
   per forward (per_forward_tables), a handful of tiny library GEMMs on the device:
     shared-MLP pre-activations of the fixed style for all SPADEs:   fixed @ Ws^T + bs
     constant-style SPADEs -> per-(sample, channel) affine  ab = (sc * (1+gamma), sh * (1+gamma) + beta)
@@ -15,28 +15,46 @@ Everything here is *exact* algebra on the reference's eval-mode forward
 """
 import ctypes
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
 from ... import _lib
 from ..._stages import stage
+from .fragment_pack import _pad, pack_matrix, pack_stream_bf16, pack_stream_x2, pack_tiles_x2c
 
 SHARED = 128
 EPS_BN = 1e-5
 
 
-def pack_matrix(w_out_in, KB, NT):
-    """[n_out, n_in] (reference layout) -> packed [NT*KB*64*4] fp32, same bytes as h3d_pack_matrix."""
-    n_out, n_in = w_out_in.shape
-    wt = torch.zeros(8 * KB, 32 * NT, dtype=torch.float32, device=w_out_in.device)
-    wt[:n_in, :n_out] = w_out_in.t().float()
-    return wt.view(KB, 2, 4, NT, 32).permute(3, 0, 1, 4, 2).contiguous().flatten()
+class _Engine(NamedTuple):
+    """One arithmetic engine of the synthesis network: the plan it runs on and its entry points of the C ABI (include/h3d.h)."""
+    name: str
+    family: str                    # "register" (build_x3), "lds" (LDS-resident activations: build_x3t) or "f32" (build_f32)
+    elem: torch.dtype              # element type of the weights' hi halves
+    fmt: str                       # weight format: "x3" hi + lo halves, "x2" f16 hi + fp6 records, "f32"
+    tier: tuple                    # (dtype code, products code): trailing arguments of the LDS-resident entry points
+    entry: str                     # the plain launch
+    flagged: Optional[str]         # the launch that takes the per-item flags: an x2 engine raises them, any other runs where one is up
+    behind: Optional[str]          # x2 engines: the engine launched behind it on those flags
+    elsewhere: Optional[str]       # register engines: the engine that takes a geometry h3d_synthesis_x3_geometry_ok rejects
 
 
-def _pad(v, n):
-    out = torch.zeros(n, dtype=torch.float32, device=v.device)
-    out[: v.numel()] = v.flatten().float()
-    return out
+_T, _TG = "h3d_synthesis_x3t_tier", "h3d_synthesis_x3t_tier_guarded"
+# "f16x2" one f16 product + one block-scaled fp6 product (both cross terms) per contraction, register-resident activations
+# (C <= 256); "bf16x3" split-bf16 matrix cores, register-resident activations (C <= 256); "bf16x3t" / "f16x2t" the same two
+# arithmetics with LDS-resident activations (C <= 448: MAP3DBN 384, MAP3DBN512L 420); "f32" fp32 matrix cores (anything else).
+# Opt-in reduced-precision tiers on the LDS-resident kernel (NOT within the 1e-3 budget; BASELINE config 5's "fp16 MFMA path"):
+# "f16w2t" weights f16 hi + lo, activations one f16 value (two products); "f16x1t" plain f16 products.
+_ENGINES = {e.name: e for e in (
+    _Engine("f16x2", "register", torch.float16, "x2", (), "h3d_synthesis_x2", "h3d_synthesis_x2_guarded", "bf16x3", "f16x2t"),
+    _Engine("bf16x3", "register", torch.bfloat16, "x3", (), "h3d_synthesis_x3", "h3d_synthesis_x3_if", None, "bf16x3t"),
+    _Engine("f16x2t", "lds", torch.float16, "x2", (1, 4), _T, _TG, "bf16x3t", None),
+    _Engine("bf16x3t", "lds", torch.bfloat16, "x3", (0, 3), _T, _TG, None, None),
+    _Engine("f16w2t", "lds", torch.float16, "x3", (1, 2), _T, _TG, None, None),
+    _Engine("f16x1t", "lds", torch.float16, "x3", (1, 1), _T, _TG, None, None),
+    _Engine("f32", "f32", torch.float32, "f32", (), "h3d_synthesis", None, None, None),
+)}
 
 
 def _grow(t, n):
@@ -66,25 +84,16 @@ class _Table:
         return torch.cat(self.chunks).contiguous()
 
 
-def _add_coord_input(tab, desc, w_in, b_in, HdP):
-    """The coordinate input's tables: w_in [C, 2] as two vectors, b_in; their offsets go into the descriptor."""
-    desc.w_in = tab.add(torch.cat([_pad(w_in[:, 0], HdP), _pad(w_in[:, 1], HdP)]))
-    desc.b_in = tab.add(_pad(b_in, HdP))
-
-
 def _rgb_table(wr, br, HdP):
     """A ToRGB layer's table: the three weight rows padded to HdP, then the bias padded to 4."""
     return torch.cat([_pad(wr[0], HdP), _pad(wr[1], HdP), _pad(wr[2], HdP), _pad(br, 4)])
 
 
-def _copy_layout(src, dst):
-    """The fields of the base descriptor that every engine's descriptor shares: per block skip / to_rgb, per SPADE its style
-    kind and its indices into the per-forward tables."""
-    for k in range(src.n_blocks):
-        dst.block[k].skip, dst.block[k].to_rgb = src.block[k].skip, src.block[k].to_rgb
-        for s in range(2):
-            d, so = dst.block[k].spade[s], src.block[k].spade[s]
-            d.pixel_style, d.g_offset, d.cst_index, d.ab_index = so.pixel_style, so.g_offset, so.cst_index, so.ab_index
+def _vec_table(raw, HdP, carry=None):
+    """A per-pixel-style SPADE's table: 1 + gamma bias, beta bias, BatchNorm scale, BatchNorm shift (with the carry of a folded
+    conv bias moved into it: build_x3), each padded to HdP."""
+    sc, sh = _pad(raw["sc"], HdP), _pad(raw["sh"], HdP)
+    return torch.cat([_pad(raw["bgam"] + 1.0, HdP), _pad(raw["bbet"], HdP), sc, sh if carry is None else sh + sc * carry])
 
 
 class SpadeDesc(ctypes.Structure):
@@ -104,7 +113,8 @@ class SynthDesc(ctypes.Structure):
 
 
 class SynthesisPlan:
-    """Packed weights + launch descriptor + the small dense matrices used by per_forward_tables."""
+    """The parsed network (dense tensors + layout descriptor), the small dense matrices used by per_forward_tables, and one
+    packed plan per engine family, built on first use: build_x3 / build_x3t / build_f32."""
 
     def __init__(self, state, prefix, input_prefix, n_blocks, mod_blocks, map3d_mode, device):
         g = lambda k: state[k].detach().to(device=device, dtype=torch.float32)
@@ -123,22 +133,17 @@ class SynthesisPlan:
         # the padded channels (its table holds 1 + gamma's bias: that entry is zero as well), conv_0's padded K columns zero.
         # Every engine then sees an ordinary C-wide network.
         self.C, self.F, self.Cin = C, F, Cin
-        HdP = (C + 31) // 32 * 32
-        self.HdP = HdP
-        NT, KBH = HdP // 32, HdP // 8
-        tab = _Table(1)
-        add = tab.add
-        desc = SynthDesc()
-        desc.n_blocks, desc.C = n_blocks, C
+        self.HdP = (C + 31) // 32 * 32
         self._w_in = _grow(g(f"{input_prefix}.network.0.weight").reshape(Cin, 2), C)
         self._b_in = _grow(g(f"{input_prefix}.network.0.bias"), C)
-        _add_coord_input(tab, desc, self._w_in, self._b_in, HdP)
+        # the layout descriptor: per block skip / to_rgb, per SPADE its style kind and its indices into the per-forward tables;
+        # every builder copies it and adds its own offsets
+        self.desc = desc = SynthDesc()
+        desc.n_blocks, desc.C = n_blocks, C
         ws_all, bs_all, self.pixel_ids, self.const_ids = [], [], [], []
-        self._raw = []          # per SPADE: dict of dense fp32 tensors (consumed by the x3 builder)
-        self._rgb = {}
-        wg_c, bg_c, wb_c, bb_c, sc_c, sh_c = [], [], [], [], [], []
+        self._raw = []          # per SPADE: dict of dense fp32 tensors (what the builders pack)
+        self._rgb = {}          # block -> ToRGB (weight [3, C], bias [3])
         for k in range(n_blocks):
-            pixel = map3d_mode == "all" or k in mod_blocks
             bd = desc.block[k]
             bd.skip = int(k >= n_blocks // 2)
             bd.to_rgb = int(k >= n_blocks // 2 - 1)
@@ -160,33 +165,19 @@ class SynthesisPlan:
                     sc, sh, wgam, wbet, bbet = (_grow(t, C) for t in (sc, sh, wgam, wbet, bbet))
                     bgam = torch.cat([bgam, bgam.new_full((C - cin,), -1.0)])      # 1 + bias is what the tables hold
                     w = torch.cat([w, w.new_zeros(C, C - cin)], dim=1)
+                pixel = map3d_mode == "all" or k in mod_blocks
                 self._raw.append(dict(pixel=pixel, conv_w=w / sigma, conv_b=g(cv + ".bias"), wgam=wgam, bgam=bgam,
                                       wbet=wbet, bbet=bbet, sc=sc, sh=sh))
                 d = bd.spade[s]
-                d.w_conv = add(pack_matrix(w / sigma, KBH, NT))
-                d.b_conv = add(_pad(g(cv + ".bias"), HdP))
                 if pixel:
-                    d.pixel_style = 1
-                    d.g_offset = SHARED * len(self.pixel_ids)
-                    d.cst_index = len(self.pixel_ids)
+                    d.pixel_style, d.g_offset, d.cst_index = 1, SHARED * len(self.pixel_ids), len(self.pixel_ids)
                     self.pixel_ids.append(sid)
-                    d.w_gamma = add(pack_matrix(wgam, SHARED // 8, NT))
-                    d.w_beta = add(pack_matrix(wbet, SHARED // 8, NT))
-                    d.vec = add(torch.cat([_pad(bgam + 1.0, HdP), _pad(bbet, HdP), _pad(sc, HdP), _pad(sh, HdP)]))
                 else:
-                    d.pixel_style = 0
-                    d.ab_index = len(self.const_ids)
+                    d.pixel_style, d.ab_index = 0, len(self.const_ids)
                     self.const_ids.append(sid)
-                    wg_c.append(wgam.t().contiguous()); bg_c.append(bgam)
-                    wb_c.append(wbet.t().contiguous()); bb_c.append(bbet)
-                    sc_c.append(sc); sh_c.append(sh)
             if bd.to_rgb:
                 tr = f"{prefix}.to_rgbs.m3d_{k}.linear"
-                wr = g(tr + ".weight").reshape(3, C)
-                self._rgb[k] = (wr, g(tr + ".bias"))
-                bd.w_rgb = add(_rgb_table(*self._rgb[k], HdP))
-        self.desc = desc
-        self.blob = tab.cat()
+                self._rgb[k] = (g(tr + ".weight").reshape(3, C), g(tr + ".bias"))
         self.ws_all = torch.stack(ws_all)                                 # [2*nb, 128, F]
         self.bs_all = torch.stack(bs_all)                                 # [2*nb, 128]
         pix = torch.tensor(self.pixel_ids, dtype=torch.long, device=device)
@@ -196,29 +187,22 @@ class SynthesisPlan:
         self.ws_pixel_t = (self.ws_all[pix].reshape(-1, F).t().contiguous() if len(self.pixel_ids) else None)
         self.ws_pixel = (self.ws_all[pix].reshape(-1, F).contiguous() if len(self.pixel_ids) else None)       # [128 np, F] rows = outputs
         if self.const_ids:
-            self.wg_c, self.bg_c = torch.stack(wg_c), torch.stack(bg_c)   # [nc,128,C], [nc,C]
-            self.wb_c, self.bb_c = torch.stack(wb_c), torch.stack(bb_c)
-            self.sc_c, self.sh_c = torch.stack(sc_c), torch.stack(sh_c)
+            const = lambda key: torch.stack([self._raw[i][key] for i in self.const_ids])
+            self.wg_c, self.bg_c = const("wgam").transpose(1, 2).contiguous(), const("bgam")    # [nc,128,C], [nc,C]
+            self.wb_c, self.bb_c = const("wbet").transpose(1, 2).contiguous(), const("bbet")
+            self.sc_c, self.sh_c = const("sc"), const("sh")
         self.g_channels = SHARED * len(self.pixel_ids)
         self.device = device
-        self._x3 = None
-        self._x2 = None
-        self._x3t = None
-        # Arithmetic engine: "f16x2" one f16 product + one block-scaled fp6 product (both cross terms) per contraction,
-        # register-resident activations (C <= 256); "bf16x3" split-bf16 matrix cores, register-resident activations (C <= 256);
-        # "bf16x3t" split-bf16 matrix cores, LDS-resident activations (C <= 448: MAP3DBN 384, MAP3DBN512L 420);
-        # "f32" fp32 matrix cores (anything else).  Opt-in reduced-precision tiers on the bf16x3t kernel (NOT within the
-        # 1e-3 budget; BASELINE config 5's "fp16 MFMA path"): "f16w2t" weights f16 hi + lo, activations one f16 value (two
-        # products); "f16x1t" plain f16 products.
+        self._x3 = self._x2 = self._x3t = self._f32 = None          # the plans, built on first use
         default = ("f16x2" if self.x2_supported() else "bf16x3" if self.x3_supported()
                    else ("f16x2t" if self.x2_weights_in_range() else "bf16x3t") if self.x3t_supported() else "f32")
         self._x2_flag = None          # int32 [B] on the device: the x2 engine's per-item range / monitor flags of the LAST run (see run())
         self.x2_guard = os.environ.get("H3D_SYNTH_GUARD", "1") != "0"
-        # Sampled error monitor of the x2 register engine (round 5): every forward re-evaluates `x2_monitor_tiles` of its
-        # 128-pixel tiles per image on the fp32-class engine and raises the item's device flag (the range guard's) when a sampled
-        # pixel differs by more than `x2_monitor_tol` of the image's channel maximum -- the bf16 engine behind it then redoes THAT
-        # ITEM (round 6: one flag per item; rounds 4-5 redid the batch, so an image depended on its batch mates).
-        # The tolerance carries the sampling factor (round 6): over 192 bench-size images the full-image maximum of |x2 - x3| was
+        # Sampled error monitor of the x2 register engine: every forward re-evaluates `x2_monitor_tiles` of its 128-pixel tiles
+        # per image on the fp32-class engine and raises the item's device flag (the range guard's) when a sampled pixel differs by
+        # more than `x2_monitor_tol` of the image's channel maximum -- the bf16 engine behind it then redoes THAT ITEM (one flag
+        # per item: an image must not depend on its batch mates).
+        # The tolerance carries the sampling factor: over 192 bench-size images the full-image maximum of |x2 - x3| was
         # 1.2 - 1.65 times the maximum over a 16-tile sample (profiles/r5_x2_fullimage_error.txt: 9.6e-4 full vs 6.6e-4 sampled,
         # 5.7e-4 vs 3.5e-4, 5.2e-4 vs 3.2e-4), so a sample is held to X2_MONITOR_BUDGET / X2_SAMPLING_FACTOR = 6e-4 / 1.7 = 3.5e-4:
         # an item whose sample passes has a full-image error of <= 6e-4 by that ratio, 40 % inside the 1e-3 budget.
@@ -227,30 +211,17 @@ class SynthesisPlan:
         self.x2_monitor_tol = float(os.environ.get("H3D_SYNTH_MONITOR_TOL", self.X2_MONITOR_BUDGET / self.X2_SAMPLING_FACTOR))
         self.x2_monitor_tiles = int(os.environ.get("H3D_SYNTH_MONITOR_TILES", "32"))
         self._x2_monitor_buf = None   # (scratch image [B,3,H,W], per-item sampled error [B]) of the last run
-        self.engine = os.environ.get("H3D_SYNTH_PRECISION", default)
+        self.engine = os.environ.get("H3D_SYNTH_PRECISION", default)          # a name of _ENGINES
 
     X2_MONITOR_BUDGET = 6e-4      # full-image |x2 - x3| an item may carry, relative to its channel maximum (budget 1e-3)
     X2_SAMPLING_FACTOR = 1.7      # largest measured (full-image maximum) / (sampled maximum) of that error, rounded up
 
-    # ------------------------------------------------------------------ split-bf16 ("x3") engine
+    # ------------------------------------------------------------------ which engines take this network
     def x3_supported(self):
-        """C <= 256, per-pixel styles only in a leading run of whole blocks before the first skip block, every block after
-        the first skip block has a skip connection too (csrc/synthesis_x3.hip)."""
-        if self.C > 256:
-            return False
-        seen_skip, seen_const = False, False
-        for k in range(self.n_blocks):
-            if seen_skip and not self.desc.block[k].skip:
-                return False
-            seen_skip = seen_skip or bool(self.desc.block[k].skip)
-            px = [bool(self.desc.block[k].spade[s].pixel_style) for s in range(2)]
-            if seen_skip and any(px):
-                return False
-            if any(px) and (seen_const or not all(px)):          # per-pixel styles: a leading run of whole blocks
-                return False
-            seen_const = seen_const or not any(px)
-        # LDS budget of csrc/synthesis_x3.hip (tables, per-sample tables, descriptor copy, 4-deep weight ring): the kernel's own count
-        return self._x3_fits(False)
+        """The register engines' structural rules (asked of the library that enforces them at launch: C <= 256, per-pixel
+        styles only in a leading run of whole blocks before the first skip block, no plain block after it) and the LDS budget of
+        csrc/synthesis_x3.hip (tables, per-sample tables, descriptor copy, weight ring): the kernel's own count."""
+        return _lib.load().h3d_synthesis_x3_structure(ctypes.byref(self.desc), 0) == 0 and self._x3_fits(False)
 
     def _x3_fits(self, x2):
         x3 = self.build_x3(bool(x2))           # the plan that would run: an x2 plan with ToRGB heads has its own table set
@@ -279,135 +250,43 @@ class SynthesisPlan:
             return False
         return self._x3_fits(True) and self.x2_weights_in_range()
 
-    @staticmethod
-    def pack_stream_bf16(w_out_in, KS, NT, acc_order=True, dtype=torch.bfloat16):
-        """[n_out, n_in] -> bf16 (or `dtype`) hi/lo weight-stream stages [KS][NT][2][64][8] (as int16 bit patterns).
-
-        acc_order (every matrix of the x3 synthesis engine: its inputs are always previous accumulators): the K dimension
-        runs in accumulator-register order, feature of k-slot (h, e) of k-step ks =
-        32*(ks//2) + (e & 3) + 8*(2*(ks & 1) + (e >> 2)) + 4*h, so that a lane's accumulator registers are its B-fragment
-        elements (csrc/synthesis_x3.hip); otherwise the natural order 16*ks + 8*h + e."""
-        n_out, n_in = w_out_in.shape
-        dev = w_out_in.device
-        wp = torch.zeros(32 * NT, 16 * KS, dtype=torch.float32, device=dev)
-        wp[:n_out, :n_in] = w_out_in.float()
-        if acc_order:
-            ks = torch.arange(KS, device=dev).view(KS, 1, 1)
-            hh = torch.arange(2, device=dev).view(1, 2, 1)
-            e = torch.arange(8, device=dev).view(1, 1, 8)
-            k = 32 * (ks // 2) + (e & 3) + 8 * (2 * (ks & 1) + (e >> 2)) + 4 * hh          # [KS, 2, 8]
-            wp = wp[:, k.reshape(-1)]
-        hi = wp.to(dtype)
-        lo = (wp - hi.float()).to(dtype)
-
-        def frag(t):        # [N, K] -> [KS, NT, 64 lanes, 8]; lane = 32*h + j, element e: n = 32nt + j, k-slot (ks, h, e)
-            return t.view(NT, 32, KS, 2, 8).permute(2, 0, 3, 1, 4).reshape(KS, NT, 64, 8)
-
-        return torch.stack([frag(hi), frag(lo)], dim=2).contiguous().view(torch.int16).flatten()
-
-    @staticmethod
-    def e2m3_codes(v):
-        """fp32 tensor -> 6-bit e2m3 codes (int64): round-to-nearest-even on the code grid, saturating at 7.5 (the same
-        arithmetic as csrc/field_pack.hpp: e2m3_code and as v_cvt_scalef32_pk32_fp6_f16)."""
-        a = v.abs().clamp(max=7.5)
-        step = torch.where(a < 2, torch.full_like(a, 0.125), torch.where(a < 4, torch.full_like(a, 0.25), torch.full_like(a, 0.5)))
-        q = torch.round(a / step) * step
-        code = torch.where(q < 2, q * 8, torch.where(q < 4, 16 + (q - 2) * 4, 24 + (q - 4) * 2)).to(torch.int64)
-        return code | ((v < 0).to(torch.int64) << 5)
-
-    @classmethod
-    def pack_stream_x2(cls, w_out_in, KS, NT, acc_order=True, dense=True):
-        """[n_out, n_in] -> weight-stream stages of the x2 engines, [KS][NT][1 KiB f16 hi fragment | 1 KiB half of the fp6
-        records] as int16 bit patterns (csrc/x3_common.hpp).  K in accumulator-register order.  The fp6 record of a lane
-        (output row n = 32 nt + lane % 32, half h = lane // 32) and K-tile T holds, for the lane's 16 input features (k-steps
-        2T, 2T+1), slots 0-15 = q6(hi * alpha), slots 16-31 = q6(lo * 2^12 * alpha) (alpha the largest power of two with
-        max|hi| * alpha <= 7.5 and no saturated lo code), six bits per slot, then the e8m0 byte of 1 / alpha four times: 7 dwords.
-        Code dwords 0-3 travel in the even k-step's stage, 16 B per lane.  The odd k-step's KiB holds, `dense` (the register
-        engine, csrc/x3_common.hpp: gemm_x2_roll reads it with one 64-bit and one 32-bit LDS load per lane, bank-conflict-free in
-        this layout), code dwords 4-5 as [64 lanes][8 B], the scale dwords as [64 lanes][4 B] and 256 B of zeros; otherwise (the
-        LDS-resident engine, which pulls 16 B per lane straight from L2) dwords 4-7 = codes, scale, scale at 16 B per lane."""
-        assert KS % 2 == 0
-        n_out, n_in = w_out_in.shape
-        dev = w_out_in.device
-        wp = torch.zeros(32 * NT, 16 * KS, dtype=torch.float32, device=dev)
-        wp[:n_out, :n_in] = w_out_in.float()
-        ks = torch.arange(KS, device=dev).view(KS, 1, 1)
-        hh = torch.arange(2, device=dev).view(1, 2, 1)
-        e = torch.arange(8, device=dev).view(1, 1, 8)
-        k = 32 * (ks // 2) + (e & 3) + 8 * (2 * (ks & 1) + (e >> 2)) + 4 * hh          # [KS, 2, 8]
-        if acc_order:
-            wp = wp[:, k.reshape(-1)]                                                  # columns now [ks][h][e]
-        # (natural order, k = 16 ks + 8 h + e, already is [ks][h][e])
-        hi16 = wp.to(torch.float16)
-        hi = hi16.float()
-        lo = wp - hi
-        N, T = 32 * NT, KS // 2
-        hi_frag = hi16.view(NT, 32, KS, 2, 8).permute(2, 0, 3, 1, 4).reshape(KS, NT, 64, 8).contiguous().view(torch.int16)
-        # slot groups: [N, T, j, h, e] -> [N, T, h, (j, e)]
-        grp = lambda t: t.view(N, T, 2, 2, 8).permute(0, 1, 3, 2, 4).reshape(N, T, 2, 16)
-        gh, gl = grp(hi), grp(lo)
-        mx = gh.abs().amax(dim=-1)
-        ea = torch.where(mx > 0, torch.floor(torch.log2(7.5 / mx.clamp_min(1e-38))), torch.zeros_like(mx)).clamp(-100, 100)
-        # no saturated lo code: one step for normal hi values (|lo| <= 2^-11 |hi|), several when hi is an f16 subnormal
-        lo_max = gl.abs().amax(dim=-1) * 4096.0
-        need = torch.where(lo_max > 0, torch.ceil(torch.log2(lo_max.clamp_min(1e-38) / 7.5)), torch.full_like(lo_max, -200.0))
-        ea = torch.minimum(ea, -need).clamp(-100, 100)
-        alpha = torch.exp2(ea).unsqueeze(-1)
-        codes = cls.e2m3_codes(torch.cat([gh * alpha, gl * alpha * 4096.0], dim=-1))    # [N, T, 2, 32]
-        c = codes.view(N, T, 2, 8, 4)
-        b0 = c[..., 0] | ((c[..., 1] & 3) << 6)
-        b1 = (c[..., 1] >> 2) | ((c[..., 2] & 15) << 4)
-        b2 = (c[..., 2] >> 4) | (c[..., 3] << 2)
-        rec = torch.zeros(N, T, 2, 32, dtype=torch.uint8, device=dev)
-        rec[..., :24] = torch.stack([b0, b1, b2], dim=-1).reshape(N, T, 2, 24).to(torch.uint8)
-        rec[..., 24:32] = (127 - ea).to(torch.uint8).unsqueeze(-1)      # dword 6, and again in dword 7 (the register engine reads it there)
-        # [N = (nt, j32), T, h, (half, 16 B)] -> stage [ks = 2T + half][nt][lane = 32 h + j32][16 B]
-        rec = rec.view(NT, 32, T, 2, 2, 16).permute(2, 4, 0, 3, 1, 5).reshape(KS, NT, 64 * 16)
-        if dense:
-            odd = rec[1::2].reshape(T, NT, 64, 16)
-            rec[1::2] = torch.cat([odd[..., 0:8].reshape(T, NT, 512), odd[..., 8:12].reshape(T, NT, 256),
-                                   odd.new_zeros(T, NT, 256)], dim=-1)
-        out = torch.empty(KS, NT, 2, 1024, dtype=torch.uint8, device=dev)
-        out[:, :, 0] = hi_frag.reshape(KS, NT, 64 * 8).view(torch.uint8).reshape(KS, NT, 1024)
-        out[:, :, 1] = rec
-        return out.view(torch.int16).flatten()
-
-    @classmethod
-    def pack_tiles_x2c(cls, w_out_in, KS, NT, acc_order=True):
-        """[n_out, n_in] -> the x2 tier's weights of the LDS-resident engine in the x2c format (round 6, csrc/x3t_common.hpp), tile-major
-        [NT][K-tile T][3 KiB] as int16 bit patterns: +0 the f16 hi fragment of k-step 2T, +1024 the lo record -- 16 B per lane: the
-        16 six-bit codes of lo * 2^12 * alpha (dwords 3-5 of the fp6 A operand) and a dword holding the lane's block-scale byte --, +2048 the hi
-        fragment of k-step 2T + 1.  The 16 hi codes (dwords 0-2) are not stored: the kernel converts them from the hi fragments
-        (v_cvt_scalef32_pk32_fp6_f16, the lane's scale), so a weight costs 3 bytes of the vector-memory path instead of 4."""
-        st = cls.pack_stream_x2(w_out_in, KS, NT, acc_order=acc_order, dense=False).view(torch.uint8).view(KS, NT, 2, 64, 16)
-        T = KS // 2
-        ev, od = st[0::2], st[1::2]                                   # [T, NT, plane, 64 lanes, 16 B]
-        rec = torch.cat([ev[:, :, 1, :, 12:16], od[:, :, 1, :, 0:9], torch.zeros_like(od[:, :, 1, :, 0:3])], dim=-1)   # dwords 3 | 4, 5 | scale byte, 0, 0, 0
-        out = torch.stack([ev[:, :, 0], rec, od[:, :, 0]], dim=2)     # [T, NT, 3, 64, 16]
-        return out.permute(1, 0, 2, 3, 4).contiguous().view(torch.int16).flatten()       # [NT][T][3][64][16 B]
-
-    # ------------------------------------------------------------------ split-bf16 engine with LDS-resident activations
     def x3t_supported(self):
-        """C <= 448, per-pixel styles only in blocks without skip connection, no plain block after the first skip block
-        (csrc/synthesis_x3t.hip)."""
-        if _lib.load().h3d_synthesis_x3t_tiles(self.C) < 0:
-            return False
-        seen_skip = False
-        for k in range(self.n_blocks):
-            blk = self.desc.block[k]
-            if seen_skip and not blk.skip:
-                return False
-            seen_skip = seen_skip or bool(blk.skip)
-            if blk.skip and (blk.spade[0].pixel_style or blk.spade[1].pixel_style):
-                return False
-        return True
+        """The LDS-resident engine's structural rules, asked of the library: C <= 448, per-pixel styles only in blocks without
+        skip connection, no plain block after the first skip block (csrc/synthesis_x3t.hip)."""
+        return _lib.load().h3d_synthesis_x3t_structure(ctypes.byref(self.desc)) == 0
 
-    # engine -> (element type of the hi halves, dtype code, products code of h3d_synthesis_x3t_tier, weight format)
-    X3T_TIERS = {"bf16x3t": (torch.bfloat16, 0, 3, "x3"), "f16x2t": (torch.float16, 1, 4, "x2"),
-                 "f16w2t": (torch.float16, 1, 2, "x3"), "f16x1t": (torch.float16, 1, 1, "x3")}
+    # ------------------------------------------------------------------ the plans
+    def _descriptor(self, tab, HdP):
+        """A builder's descriptor: the layout of self.desc, and the coordinate input's tables (w_in [C, 2] as two vectors, b_in)
+        as the first entries of `tab`."""
+        desc = SynthDesc.from_buffer_copy(self.desc)
+        desc.w_in = tab.add(torch.cat([_pad(self._w_in[:, 0], HdP), _pad(self._w_in[:, 1], HdP)]))
+        desc.b_in = tab.add(_pad(self._b_in, HdP))
+        return desc
+
+    def build_f32(self):
+        """The plan of the fp32 engine: every matrix as fp32 MFMA B fragments and every table in one blob, the descriptor's
+        offsets in floats into it."""
+        if self._f32 is None:
+            HdP = self.HdP
+            NT, tab = HdP // 32, _Table(1)
+            desc = self._descriptor(tab, HdP)
+            for k in range(self.n_blocks):
+                for s in range(2):
+                    raw, d = self._raw[2 * k + s], desc.block[k].spade[s]
+                    d.w_conv = tab.add(pack_matrix(raw["conv_w"], HdP // 8, NT))
+                    d.b_conv = tab.add(_pad(raw["conv_b"], HdP))
+                    if raw["pixel"]:
+                        d.w_gamma = tab.add(pack_matrix(raw["wgam"], SHARED // 8, NT))
+                        d.w_beta = tab.add(pack_matrix(raw["wbet"], SHARED // 8, NT))
+                        d.vec = tab.add(_vec_table(raw, HdP))
+                if desc.block[k].to_rgb:
+                    desc.block[k].w_rgb = tab.add(_rgb_table(*self._rgb[k], HdP))
+            self._f32 = dict(desc=desc, blob=tab.cat(), HdP=HdP)
+        return self._f32
 
     def build_x3t(self, dtype=torch.bfloat16, fmt="x3"):
-        """Weights as bf16 (f16 for the reduced-precision tiers) hi/lo MFMA A fragments, tile-major [tile][k-step][hi|lo][64 lanes][8] (conv matrices with K in
+        """The plan of the LDS-resident engine.  Weights as bf16 (f16 for the reduced-precision tiers) hi/lo MFMA A fragments, tile-major [tile][k-step][hi|lo][64 lanes][8] (conv matrices with K in
         accumulator-register order, gamma / beta in natural order: their input is assembled from memory), fp32 tables
         padded to the engine's width 32 * tiles, and a descriptor whose w_* offsets are BYTES into the fragment blob and
         whose vec / b_conv / w_rgb / w_in / b_in offsets are FLOATS into the tables."""
@@ -415,40 +294,32 @@ class SynthesisPlan:
             self._x3t = {}
         if (dtype, fmt) in self._x3t:
             return self._x3t[(dtype, fmt)]
-        C = self.C
-        NT = _lib.load().h3d_synthesis_x3t_tiles(C)
+        NT = _lib.load().h3d_synthesis_x3t_tiles(self.C)
         HdP, KS = 32 * NT, 2 * NT
         wchunks, woff, tab = [], [0], _Table(4)
-        add_t = tab.add
 
         def add_w(w_out_in, ks, acc_order):
             o = woff[0]
             if fmt == "x2":        # x2c: f16 hi fragments + lo records, [NT][K-tile][3 KiB]
-                wchunks.append(self.pack_tiles_x2c(w_out_in, ks, NT, acc_order=acc_order))
+                wchunks.append(pack_tiles_x2c(w_out_in, ks, NT, acc_order=acc_order))
             else:
-                frag = self.pack_stream_bf16(w_out_in, ks, NT, acc_order=acc_order, dtype=dtype).view(ks, NT, 2 * 64 * 8)
+                frag = pack_stream_bf16(w_out_in, ks, NT, acc_order=acc_order, dtype=dtype).view(ks, NT, 2 * 64 * 8)
                 wchunks.append(frag.transpose(0, 1).contiguous().flatten())      # [NT][ks][2][64][8]
             woff[0] += wchunks[-1].numel() * 2
             return o
 
-        desc = SynthDesc()
-        desc.n_blocks, desc.C = self.n_blocks, C
-        _add_coord_input(tab, desc, self._w_in, self._b_in, HdP)
-        _copy_layout(self.desc, desc)
+        desc = self._descriptor(tab, HdP)
         for k in range(self.n_blocks):
-            dst = desc.block[k]
             for s in range(2):
-                raw = self._raw[2 * k + s]
-                d = dst.spade[s]
+                raw, d = self._raw[2 * k + s], desc.block[k].spade[s]
                 if raw["pixel"]:
                     d.w_gamma = add_w(raw["wgam"], SHARED // 16, False)
                     d.w_beta = add_w(raw["wbet"], SHARED // 16, False)
-                    d.vec = add_t(torch.cat([_pad(raw["bgam"] + 1.0, HdP), _pad(raw["bbet"], HdP), _pad(raw["sc"], HdP),
-                                             _pad(raw["sh"], HdP)]))
+                    d.vec = tab.add(_vec_table(raw, HdP))
                 d.w_conv = add_w(raw["conv_w"], KS, True)
-                d.b_conv = add_t(_pad(raw["conv_b"], HdP))
-            if dst.to_rgb:
-                dst.w_rgb = add_t(_rgb_table(*self._rgb[k], HdP))
+                d.b_conv = tab.add(_pad(raw["conv_b"], HdP))
+            if desc.block[k].to_rgb:
+                desc.block[k].w_rgb = tab.add(_rgb_table(*self._rgb[k], HdP))
         self._x3t[(dtype, fmt)] = dict(desc=desc, wblob=torch.cat(wchunks).contiguous(), tables=tab.cat(), NT=NT, HdP=HdP)
         return self._x3t[(dtype, fmt)]
 
@@ -467,9 +338,8 @@ class SynthesisPlan:
         return getattr(self, cache)
 
     def _build_x3(self, x2, heads):
-        pack = self.pack_stream_x2 if x2 else self.pack_stream_bf16
-        C = self.C
-        NT = 8 if C > 128 else 4
+        pack = pack_stream_x2 if x2 else pack_stream_bf16
+        NT = 8 if self.C > 128 else 4
         HdP = NT * 32
         # Conv biases are folded on the host (the x3 kernel never adds one): the kernel's activations are the true ones
         # minus a per-channel "carry" -- the bias of the conv that produced them plus, along a skip chain, the carry of
@@ -479,10 +349,7 @@ class SynthesisPlan:
         carry = torch.zeros(HdP, device=self.device, dtype=torch.float32)
         ab_carry = torch.zeros(max(1, len(self.const_ids)), HdP, device=self.device, dtype=torch.float32)
         tab = _Table(4)
-        desc = SynthDesc()
-        desc.n_blocks, desc.C = self.n_blocks, C
-        _add_coord_input(tab, desc, self._w_in, self._b_in, HdP)
-        _copy_layout(self.desc, desc)
+        desc = self._descriptor(tab, HdP)
         stream, stages = [], 0
         rgb_tables = {}                                         # block k -> (Wr [3, C], br' [3]) as written to the tables
         for k in range(self.n_blocks):
@@ -492,20 +359,18 @@ class SynthesisPlan:
             mid_block = (not src.skip and not any(self.desc.block[q].skip for q in range(k))
                          and not self._raw[2 * k]["pixel"] and not self._raw[2 * k + 1]["pixel"])
             for s in range(2):
-                raw = self._raw[2 * k + s]
-                d = desc.block[k].spade[s]
+                raw, d = self._raw[2 * k + s], desc.block[k].spade[s]
                 if raw["pixel"]:
                     stream.append(pack(raw["wgam"], SHARED // 16, NT))
                     stream.append(pack(raw["wbet"], SHARED // 16, NT))
                     stages += 2 * (SHARED // 16)
-                    sc, sh = _pad(raw["sc"], HdP), _pad(raw["sh"], HdP)
-                    d.vec = tab.add(torch.cat([_pad(raw["bgam"] + 1.0, HdP), _pad(raw["bbet"], HdP), sc, sh + sc * carry]))
+                    d.vec = tab.add(_vec_table(raw, HdP, carry))
                 else:
                     ab_carry[d.ab_index] = carry
                 if x2 and self.X2_MID_X3 and mid_block:
-                    # round 6: this convolution on three bf16 products inside the x2 kernel (csrc/synthesis_x3.hip: MIDX3): its
+                    # this convolution on three bf16 products inside the x2 kernel (csrc/synthesis_x3.hip: MIDX3): its
                     # stages in the x3 format, the SPADE marked through its (otherwise unused) g_offset
-                    stream.append(self.pack_stream_bf16(raw["conv_w"], 2 * NT, NT))
+                    stream.append(pack_stream_bf16(raw["conv_w"], 2 * NT, NT))
                     d.g_offset = 1
                 else:
                     stream.append(pack(raw["conv_w"], 2 * NT, NT))
@@ -533,7 +398,7 @@ class SynthesisPlan:
     X2_MID_X3 = True
 
     def _torgb_heads(self, desc, rgb_tables, tab, NT, HdP):
-        """x2 register engine, round 5: the ToRGB layers of the skip blocks as a NINTH output tile of each block's second
+        """x2 register engine: the ToRGB layers of the skip blocks as a NINTH output tile of each block's second
         convolution (csrc/synthesis_x3.hip: conv_progressive HEAD).  With x_k = x_{k-1} + W1_k y_k along the skip chain (biases
         live in the carries, build_x3), sum_k Wr_k x_k over the skip blocks k >= fs that feed ToRGB is
 
@@ -565,12 +430,13 @@ class SynthesisPlan:
         desc.block[fs - 1].w_rgb = tab.add(_rgb_table(wm, bm, HdP))
         lanes = torch.tensor([0, 1, 2, 3, 32, 33, 34, 35], device=self.device)
         for j in range(fs, n):
-            st = self.pack_stream_x2(heads[j].float(), 2 * NT, 1, acc_order=True, dense=False)            # [KS][1][2][64][8] int16
+            st = pack_stream_x2(heads[j].float(), 2 * NT, 1, acc_order=True, dense=False)                 # [KS][1][2][64][8] int16
             head = st.view(2 * NT, 2, 64, 8)[:, :, lanes].contiguous()                                    # [KS][hi | rec][8 lanes][16 B]
             desc.block[j].to_rgb = 0
             desc.block[j].spade[1].b_conv = tab.add(head.view(torch.float32))
         return set(range(fs - 1, n))               # blocks whose own ToRGB table is superseded
 
+    # ------------------------------------------------------------------ per forward
     def per_forward_tables(self, feature_maps, fixed_style, HdP=None):
         """feature_maps [B,R,F] (rendered, channels last), fixed_style [B,F] -> (G, cst, ab)."""
         HdP = self.HdP if HdP is None else HdP
@@ -624,29 +490,26 @@ class SynthesisPlan:
             ab = ab.view(Bq, nq, 2, Hq // 2, 2).permute(0, 1, 3, 2, 4).contiguous()
         return G, cst, ab
 
+    def _plan(self, eng):
+        if eng.family == "register":
+            return self.build_x3(eng.fmt == "x2")
+        return self.build_x3t(eng.elem, eng.fmt) if eng.family == "lds" else self.build_f32()
+
     def _resolve(self, H, W, Hr, Wr):
-        """-> (family, plan, tier) that run() launches for this geometry: "x3" (the register engines, plan = build_x3), "x3t"
-        (the LDS-resident engine, plan = build_x3t of `tier`) or "f32" (the fp32 engine on self.blob, plan None)."""
-        if self.engine not in ("bf16x3", "f16x2", "f32") and self.engine not in self.X3T_TIERS:
+        """-> the engine (a row of _ENGINES) that run() launches for this geometry, and its plan."""
+        if self.engine not in _ENGINES:
             raise ValueError(f"unknown synthesis engine {self.engine!r}")
-        name = self.engine
-        if name in ("bf16x3", "f16x2"):
-            x3 = self.build_x3(name == "f16x2")
-            if not self.pixel_ids or _lib.load().h3d_synthesis_x3_geometry_ok(H, W, Hr, Wr):
-                return "x3", x3, None
-            # the x3 engine's matrix-core resize does not cover this geometry: the LDS-resident engine does
-            # (f16x2 falls back to the x2 tier of that engine, bf16x3 to its three-product tier)
-            name = ("f16x2t" if name == "f16x2" else "bf16x3t") if self.x3t_supported() else "f32"
-        if name == "f32":
-            return "f32", None, None
-        tier = self.X3T_TIERS[name]
-        return "x3t", self.build_x3t(tier[0], tier[3]), tier
+        eng = _ENGINES[self.engine]
+        if eng.family == "register" and self.pixel_ids and not _lib.load().h3d_synthesis_x3_geometry_ok(H, W, Hr, Wr):
+            # the register engines' matrix-core resize does not cover this geometry: the LDS-resident engine does
+            eng = _ENGINES[eng.elsewhere if self.x3t_supported() else "f32"]
+        return eng, self._plan(eng)
 
     def _args(self, plan, G, cst, ab, rgb, B, Hr, Wr, H, W):
-        """The arguments every x3 (stream, stages, tables, table floats, ..) and x3t (weight blob, tables, ..) entry point starts
-        with, up to the image and its shape."""
+        """The arguments every x3 (stream, stages, tables, table floats, ..), x3t (weight blob, tables, ..) and fp32 (blob, ..)
+        entry point starts with, up to the image and its shape."""
         head = ((_lib.ptr(plan["stream"]), plan["stages"], _lib.ptr(plan["tables"]), plan["tables"].numel()) if "stream" in plan
-                else (_lib.ptr(plan["wblob"]), _lib.ptr(plan["tables"])))
+                else (_lib.ptr(plan["wblob"]), _lib.ptr(plan["tables"])) if "wblob" in plan else (_lib.ptr(plan["blob"]),))
         return head + (ctypes.byref(plan["desc"]), _lib.ptr(G), self.g_channels, Hr, Wr, _lib.ptr(cst), len(self.pixel_ids),
                        _lib.ptr(ab), len(self.const_ids), _lib.ptr(rgb), B, H, W)
 
@@ -655,51 +518,41 @@ class SynthesisPlan:
         B = fixed_style.shape[0]
         Hr, Wr = render_hw
         H, W = out_hw
-        family, plan, tier = self._resolve(H, W, Hr, Wr)
-        x2 = family == "x3" and self.engine == "f16x2"
+        eng, plan = self._resolve(H, W, Hr, Wr)
         with stage(owner, "synthesis_tables"):
-            if family == "x3":
-                G, cst, ab = self.x3_forward_tables(feature_maps.float(), fixed_style.float(), x2)
+            if eng.family == "register":
+                G, cst, ab = self.x3_forward_tables(feature_maps.float(), fixed_style.float(), eng.fmt == "x2")
             else:
-                G, cst, ab = self.per_forward_tables(feature_maps.float(), fixed_style.float(), plan["HdP"] if plan else None)
+                G, cst, ab = self.per_forward_tables(feature_maps.float(), fixed_style.float(), plan["HdP"])
         rgb = torch.empty(B, 3, H, W, device=fixed_style.device, dtype=torch.float32)
-        what = {"x3": "h3d_synthesis_x2" if x2 else "h3d_synthesis_x3", "x3t": "h3d_synthesis_x3t", "f32": "h3d_synthesis"}[family]
         lib, st = _lib.load(), _lib.stream_handle()
-        args = lambda p, img=rgb: self._args(p, G, cst, ab, img, B, Hr, Wr, H, W)
+
+        def call(name, *a):
+            _lib.check(getattr(lib, name)(*a, st), name)          # the error names the call that failed
+
+        def launch(name, p, *tail, img=rgb):
+            call(name, *self._args(p, G, cst, ab, img, B, Hr, Wr, H, W), *tail)
+
         with stage(owner, "synthesis"):
-            if family == "x3t" and tier[2] == 4 and self.x2_guard:
-                # the x2 tier of the LDS-resident engine, range-guarded like the register engine below: the bf16 tier runs
-                # behind it on the same flag and only does work when the x2 launch left its f16 range
-                alt_tier = self.X3T_TIERS["bf16x3t"]
-                alt = self.build_x3t(alt_tier[0], alt_tier[3])
-                flag = _lib.ptr(self._flags(B, fixed_style.device))
-                rc = lib.h3d_synthesis_x3t_tier_guarded(*args(plan), tier[1], tier[2], flag, st) or \
-                    lib.h3d_synthesis_x3t_tier_guarded(*args(alt), alt_tier[1], alt_tier[2], flag, st)
-            elif family == "x3t":
-                rc = lib.h3d_synthesis_x3t_tier(*args(plan), tier[1], tier[2], st)
-            elif x2 and self.x2_guard:
+            if eng.behind is None or not self.x2_guard:
+                launch(eng.entry, plan, *eng.tier)
+            else:
                 # Range-guarded x2: the kernel raises an item's device flag when an activation of that item leaves the range
                 # its f16 planes carry (|x| >= 2^15, inf, NaN upstream); the bf16 engine, launched right behind it on the same
-                # stream, skips the items whose flag is clear and recomputes the others.  No host synchronisation; the x3
-                # stream shares descriptor, tables and per-forward tables with the x2 one (only the weight format differs).
-                alt = self.build_x3(False)
+                # stream, skips the items whose flag is clear and recomputes the others.  No host synchronisation; on the register
+                # engines the x3 stream shares descriptor, tables and per-forward tables with the x2 one (only the weight format
+                # differs).
+                behind = _ENGINES[eng.behind]
+                alt = self._plan(behind)
                 flag = _lib.ptr(self._flags(B, fixed_style.device))
-                rc = lib.h3d_synthesis_x2_guarded(*args(plan), flag, st)
-                if not rc and self.x2_monitor:
-                    what = "h3d_synthesis_x3_tiles / h3d_synthesis_check"
+                launch(eng.flagged, plan, *eng.tier, flag)
+                if eng.family == "register" and self.x2_monitor:
                     first, step = self.monitor_tiles(H, W)
                     buf = self._monitor_buf(rgb)
-                    rc = lib.h3d_synthesis_x3_tiles(*args(alt, buf[0]), first, step, st)
-                    rc = rc or lib.h3d_synthesis_check(_lib.ptr(rgb), _lib.ptr(buf[0]), B, H, W, first, step, self.x2_monitor_tol,
-                                                       flag, _lib.ptr(buf[1]), _lib.ptr(buf[2]), st)
-                if not rc:
-                    what = "h3d_synthesis_x3_if"
-                    rc = lib.h3d_synthesis_x3_if(*args(alt), flag, st)
-            elif family == "x3":
-                rc = (lib.h3d_synthesis_x2 if x2 else lib.h3d_synthesis_x3)(*args(plan), st)
-            else:
-                rc = self._launch(G, cst, ab, rgb, B, Hr, Wr, H, W)
-        _lib.check(rc, what)
+                    launch("h3d_synthesis_x3_tiles", alt, first, step, img=buf[0])
+                    call("h3d_synthesis_check", _lib.ptr(rgb), _lib.ptr(buf[0]), B, H, W, first, step, self.x2_monitor_tol, flag,
+                         _lib.ptr(buf[1]), _lib.ptr(buf[2]))
+                launch(behind.flagged, alt, *behind.tier, flag)
         return rgb
 
     def _monitor_buf(self, rgb):
@@ -743,8 +596,3 @@ class SynthesisPlan:
     def x2_fallback_items(self):
         """Batch indices the bf16 engine redid in the last guarded run (synchronises)."""
         return [] if self._x2_flag is None else torch.nonzero(self._x2_flag).flatten().tolist()
-
-    def _launch(self, G, cst, ab, rgb, B, Hr, Wr, H, W):
-        return _lib.load().h3d_synthesis(_lib.ptr(self.blob), ctypes.byref(self.desc), _lib.ptr(G), self.g_channels, Hr, Wr,
-                                       _lib.ptr(cst), len(self.pixel_ids), _lib.ptr(ab), len(self.const_ids),
-                                       _lib.ptr(rgb), B, H, W, _lib.stream_handle())

@@ -468,6 +468,12 @@ int h3d_synthesis(const void* blob, const h3d_synth_desc* desc, const float* G, 
  * Returns H3D_EUNSUPPORTED (use h3d_synthesis) for C > 256, a per-pixel-style block after the first skip block, a
  * block without skip connection after the first one that has it, or (with per-pixel-style blocks) a geometry
  * h3d_synthesis_x3_geometry_ok rejects. */
+/* HOST helper, no HIP call: the structural part of that answer, from the descriptor's layout alone (n_blocks, C, skip and
+ * pixel_style flags; no offset or index is read) -- H3D_OK, or H3D_EUNSUPPORTED with the launch's own error text for C > 256, a
+ * block without skip connection after the first skip block, a per-pixel-style SPADE in or after the first skip block, or
+ * per-pixel-style SPADEs that are not a leading run of whole blocks.  h3d_synthesis_x3 / _x2 and their variants validate with
+ * the same code.  x2: 0 asks for h3d_synthesis_x3, 1 for h3d_synthesis_x2; the two engines share every rule. */
+int h3d_synthesis_x3_structure(const h3d_synth_desc* desc, int x2);
 /* 1 when the x3 engine's matrix-core bilinear resize covers this geometry (only needed with per-pixel-style blocks):
  * W a multiple of 32 and 32 consecutive output pixels touching at most 8 low-res columns (31*Wr < 6*W). */
 int h3d_synthesis_x3_geometry_ok(int H, int W, int Hr, int Wr);
@@ -488,7 +494,7 @@ int h3d_synthesis_x3(const void* stream, int64_t total_stages, const float* tabl
  * finite) -- the reference trains them under fp16 autocast (lib/trainers/base_trainer.py:50-51); h3d_synthesis_x2_guarded
  * below detects a violation.  Same arguments, limits and return codes as
  * h3d_synthesis_x3; the stream holds, per stage, [tile][1 KiB f16 hi fragment][1 KiB half of the K-tile's fp6 records]
- * (record layout as for h3d_field_pack_x2; SynthesisPlan.pack_stream_x2), and the kernel needs
+ * (record layout as for h3d_field_pack_x2; lib/generators/fragment_pack.py: pack_stream_x2), and the kernel needs
  * h3d_synthesis_x2_extra_lds(C) more bytes of LDS than h3d_synthesis_x3 (one more ring buffer).
  * ToRGB heads (round 5, x2 plans only): a skip block whose spade[1].b_conv is >= 0 (this engine folds conv biases on
  * the host, so the field is free) carries at that FLOAT offset of `tables` a 4 KB table [k-step][f16 hi fragment | half of the
@@ -561,6 +567,9 @@ int h3d_synthesis_check(const float* rgb, const float* rgb_ref, int B, int H, in
  * for C > 448, a per-pixel-style SPADE inside a skip block, or a block without skip connection after the first one
  * that has it. */
 int h3d_synthesis_x3t_tiles(int C);
+/* HOST helper, no HIP call: those three rules on the descriptor's layout alone (n_blocks, C, skip and pixel_style flags) --
+ * H3D_OK or H3D_EUNSUPPORTED with the launch's own error text; the launches validate with the same code. */
+int h3d_synthesis_x3t_structure(const h3d_synth_desc* desc);
 int h3d_synthesis_x3t(const void* wblob, const float* tables, const h3d_synth_desc* desc, const float* G, int g_channels,
                       int Hr, int Wr, const float* cst, int n_cst, const float* ab, int n_ab, float* rgb, int B, int H,
                       int W, h3d_stream_t stream);

@@ -8,7 +8,7 @@ from conftest import load_golden
 
 gens = importlib.import_module("3dhumangan_amd.lib.generators")
 impl = importlib.import_module("3dhumangan_amd.lib.implicit_funcitions")
-pack = importlib.import_module("3dhumangan_amd.lib.generators.synthesis_pack")
+pack = importlib.import_module("3dhumangan_amd.lib.generators.fragment_pack")
 h3dlib = importlib.import_module("3dhumangan_amd._lib")
 configs = importlib.import_module("3dhumangan_amd.configs")
 

@@ -16,7 +16,7 @@ from conftest import load_golden, rel_err
 gens = importlib.import_module("3dhumangan_amd.lib.generators")
 impl = importlib.import_module("3dhumangan_amd.lib.implicit_funcitions")
 pack = importlib.import_module("3dhumangan_amd.lib.generators.style_input_pack")
-spack = importlib.import_module("3dhumangan_amd.lib.generators.synthesis_pack")
+spack = importlib.import_module("3dhumangan_amd.lib.generators.fragment_pack")
 
 GOLDENS = ["gen_tiny_norender_segments", "gen_tiny_norender_semantics", "gen_tiny_norender_none"]
 TOL = 5e-5          # the bar of the oracle-vs-golden tests: the goldens are fp32 results of the reference

@@ -10,16 +10,13 @@ import torch
 
 import h3d_oracle as O
 from conftest import rel_err
+from x2_emulation import acc_k
 
 L = importlib.import_module("3dhumangan_amd._lib")
 impl = importlib.import_module("3dhumangan_amd.lib.implicit_funcitions")
 
 K_SIN, K_SA = 64.0, 1.0        # input / activation scales of csrc/field_x3.hip
 W_NAMES = ["coord", "f0a", "geo", "f0b", "f1", "f2", "f3", "color", "feat"]
-
-
-def acc_k(ks, h, e):
-    return 32 * (ks // 2) + (e & 3) + 8 * (2 * (ks & 1) + (e >> 2)) + 4 * h
 
 
 def pack(net, Hd, F):

@@ -2,6 +2,8 @@
 the CPU: the packed weight stream (consumption order, accumulator-order K permutation, hi + lo halves), the folded conv
 biases / ToRGB biases and the per-forward tables are decoded and run through a plain float64 restatement of what
 csrc/synthesis_x3.hip computes, and the image must match the oracle's SynthesisNetwork.  No HIP call is made."""
+import ctypes
+import functools
 import importlib
 
 import pytest
@@ -9,14 +11,12 @@ import torch
 
 import h3d_oracle as O
 from conftest import load_golden, rel_err
+from x2_emulation import acc_k
 
 gens = importlib.import_module("3dhumangan_amd.lib.generators")
 sp = importlib.import_module("3dhumangan_amd.lib.generators.synthesis_pack")
 impl = importlib.import_module("3dhumangan_amd.lib.implicit_funcitions")
-
-
-def acc_k(ks, h, e):
-    return 32 * (ks // 2) + (e & 3) + 8 * (2 * (ks & 1) + (e >> 2)) + 4 * h
+_lib = importlib.import_module("3dhumangan_amd._lib")
 
 
 def decode_matrix(stream_i16, stage0, KS, NT):
@@ -53,7 +53,7 @@ def decode_x2(stream_i16, stage0, KS, NT, order=None, dense=True):
     groups = []
     for T in range(KS // 2):
         # even stage: code dwords 0-3 at 16 B per lane; odd stage DENSE: code dwords 4-5 as [64 lanes][8 B], scale dwords as
-        # [64 lanes][4 B], 256 B of zeros (pack_stream_x2(dense=True): conflict-free 64- / 32-bit LDS reads)
+        # [64 lanes][4 B], 256 B of zeros (fragment_pack.pack_stream_x2(dense=True): conflict-free 64- / 32-bit LDS reads)
         ev, od = half[2 * T].view(NT, 64, 16), half[2 * T + 1]
         if dense:
             assert not od[:, 768:].any()
@@ -224,3 +224,69 @@ def test_head_tables_that_do_not_fit_the_lds_leave_the_plan_on_x2_with_the_ridin
         if not heads:          # every block that feeds ToRGB kept its own table
             assert all(seg["desc"].block[j].w_rgb >= 0 for j in range(seg["desc"].n_blocks) if seg["desc"].block[j].to_rgb)
             assert sum(int(seg["desc"].block[j].to_rgb) for j in range(seg["desc"].n_blocks)) > 0
+
+
+# ---- engine eligibility: the structure entry points against the launch validation
+
+@functools.lru_cache(maxsize=None)
+def _shipped_plans():
+    """One 32-wide nine-block network (per-pixel styles in blocks 0-2, skip connections from block 4) planned in the three modes."""
+    meta = dict(load_golden("gen_tiny_mixed")["meta"])
+    meta.update(hidden_dim=32, latent_dim=32, feature_dim=32, synthesis_blocks=9, mod_blocks=[0, 1, 2])
+    meta["neural_field_cls"] = impl.COORDCONCATSIREN
+    torch.manual_seed(0)
+    sd = {k: v.detach().clone() for k, v in gens.Map3DGenerator(**meta).eval().state_dict().items()}
+    return {mode: sp.SynthesisPlan(sd, "synthesis_network", "synthesis_input", 9, (0, 1, 2), mode, torch.device("cpu"))
+            for mode in ("mixed", "isolated", "all")}
+
+
+# structure -> (the register engines take it, the LDS-resident engine takes it)
+STRUCTURES = {"mixed": (True, True), "isolated": (True, True), "all": (False, False), "pixel_in_skip": (False, False),
+              "plain_after_skip": (False, False), "half_pixel": (False, True), "C257": (False, True), "C449": (False, False)}
+
+
+def structure_desc(name):
+    """-> (SynthDesc layout, n_cst, n_ab): a shipped mode's own descriptor, or the mixed one with one thing the engines refuse."""
+    plan = _shipped_plans().get(name, _shipped_plans()["mixed"])
+    d = sp.SynthDesc.from_buffer_copy(plan.desc)
+    if name == "pixel_in_skip":               # a per-pixel SPADE inside a skip block
+        d.block[5].spade[0].pixel_style, d.block[5].spade[0].g_offset, d.block[5].spade[0].cst_index = 1, 0, 0
+    elif name == "plain_after_skip":          # a plain block after the first skip block
+        d.block[6].skip = 0
+    elif name == "half_pixel":                # a block with one per-pixel and one constant-style SPADE
+        d.block[2].spade[1].pixel_style, d.block[2].spade[1].ab_index = 0, 0
+    elif name.startswith("C"):
+        d.C = int(name[1:])
+    return d, len(plan.pixel_ids), len(plan.const_ids)
+
+
+def host_buffer():
+    buf = torch.zeros(64)
+    assert buf.data_ptr() % 16 == 0
+    return buf
+
+
+@pytest.mark.parametrize("x2", [0, 1])
+@pytest.mark.parametrize("name", list(STRUCTURES))
+def test_x3_structure_is_what_the_launch_validates(name, x2):
+    """h3d_synthesis_x3_structure (what x3_supported asks) and the launch entry points run the same rules: at B = 0 -- validation
+    only, no HIP call -- a launch on the same layout returns the same code with the same error text."""
+    lib = _lib.load()
+    desc, n_cst, n_ab = structure_desc(name)
+    rc = lib.h3d_synthesis_x3_structure(ctypes.byref(desc), x2)
+    said = lib.h3d_last_error()
+    assert rc == (0 if STRUCTURES[name][0] else -2)
+    if name in _shipped_plans():
+        assert _shipped_plans()[name].x3_supported() == (rc == 0)
+    NT = 8 if desc.C > 128 else 4
+    stages = 0
+    for k in range(desc.n_blocks):
+        for s in range(2):
+            desc.block[k].spade[s].b_conv = -1                   # folded biases, no ToRGB head tables
+            stages += 2 * NT + (16 if desc.block[k].spade[s].pixel_style else 0)
+    buf = host_buffer()
+    p = _lib.ptr(buf)
+    entry = lib.h3d_synthesis_x2 if x2 else lib.h3d_synthesis_x3
+    got = entry(p, stages, p, 0, ctypes.byref(desc), p, 128 * n_cst, 4, 4, p, n_cst, p, n_ab, p, 0, 32, 32, None)
+    assert got == rc, lib.h3d_last_error()
+    assert rc == 0 or lib.h3d_last_error() == said

@@ -3,6 +3,7 @@ CPU: the tile-major fragment blob (accumulator-order K for the convs, natural or
 fp32 tables and the per-forward tables are decoded and run through a plain float64 restatement of what
 csrc/synthesis_x3t.hip computes; the image must match the oracle's SynthesisNetwork.  Widths 384 / 420 are the ones the
 engine exists for (here at a tiny image).  No kernel launch (only the HOST helper h3d_synthesis_x3t_tiles)."""
+import ctypes
 import importlib
 
 import pytest
@@ -10,14 +11,12 @@ import torch
 
 import h3d_oracle as O
 from conftest import load_golden, rel_err
+from x2_emulation import acc_k
 
 gens = importlib.import_module("3dhumangan_amd.lib.generators")
 sp = importlib.import_module("3dhumangan_amd.lib.generators.synthesis_pack")
+fp = importlib.import_module("3dhumangan_amd.lib.generators.fragment_pack")
 impl = importlib.import_module("3dhumangan_amd.lib.implicit_funcitions")
-
-
-def acc_k(ks, h, e):
-    return 32 * (ks // 2) + (e & 3) + 8 * (2 * (ks & 1) + (e >> 2)) + 4 * h
 
 
 def decode_matrix(wblob_i16, byte_off, KS, NT, acc_order):
@@ -50,7 +49,7 @@ def decode_x2(wblob_i16, byte_off, KS, NT, acc_order):
     assert not lorec[..., 13:16].any()                                              # the scale byte alone in its dword
     alpha = torch.exp2((127 - scale_byte).double())                                # [NT, T, 64]
     hv = hi.contiguous().view(torch.float16).double().view(NT, T, 2, 64, 8).permute(0, 1, 3, 2, 4).reshape(NT, T, 64, 16)
-    codes = sp.SynthesisPlan.e2m3_codes((hv * alpha.unsqueeze(-1)).float())      # slots 0-15: 8 j + e  [NT, T, 64, 16]
+    codes = fp.e2m3_codes((hv * alpha.unsqueeze(-1)).float())      # slots 0-15: 8 j + e  [NT, T, 64, 16]
     c = codes.view(NT, T, 64, 4, 4)
     b0 = c[..., 0] | ((c[..., 1] & 3) << 6)
     b1 = (c[..., 1] >> 2) | ((c[..., 2] & 15) << 4)
@@ -155,3 +154,21 @@ def test_x3t_plan_refuses_what_the_kernel_cannot_run():
     plan = sp.SynthesisPlan(Gn.state_dict(), "synthesis_network", "synthesis_input", meta["synthesis_blocks"],
                             tuple(meta["mod_blocks"]), "all", torch.device("cpu"))
     assert not plan.x3t_supported() and plan.engine == "f32"
+
+
+def test_x3t_structure_is_what_the_launch_validates():
+    """h3d_synthesis_x3t_structure (what x3t_supported asks) and the launch entry point run the same rules: at B = 0 -- validation
+    only, no HIP call -- a launch on the same layout returns the same code with the same error text."""
+    from test_x3_plan_cpu import STRUCTURES, _shipped_plans, host_buffer, structure_desc
+    lib = importlib.import_module("3dhumangan_amd._lib")
+    for name, (_, ok) in STRUCTURES.items():
+        desc, n_cst, n_ab = structure_desc(name)
+        rc = lib.load().h3d_synthesis_x3t_structure(ctypes.byref(desc))
+        said = lib.load().h3d_last_error()
+        assert rc == (0 if ok else -2), name
+        if name in _shipped_plans():
+            assert _shipped_plans()[name].x3t_supported() == ok
+        p = lib.ptr(host_buffer())
+        got = lib.load().h3d_synthesis_x3t_tier(p, p, ctypes.byref(desc), p, 128 * n_cst, 4, 4, p, n_cst, p, n_ab, p, 0, 32, 32, 0, 3, None)
+        assert got == rc, (name, lib.load().h3d_last_error())
+        assert rc == 0 or lib.load().h3d_last_error() == said, name

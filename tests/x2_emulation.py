@@ -116,7 +116,7 @@ def x2_operands_matmul(x, Whi, groups, dynamic=True, x_scale_hi=4.0, rho=4096.0)
 
 
 def x2_weight_operands(W, rho=4096.0):
-    """What SynthesisPlan.pack_stream_x2 encodes (no matrix scale): -> (Whi, groups) for x2_operands_matmul."""
+    """What fragment_pack.pack_stream_x2 encodes (no matrix scale): -> (Whi, groups) for x2_operands_matmul."""
     W = W.double()
     Wh = f16(W)
     Wl = W - Wh
